@@ -25,6 +25,12 @@ Multi-GPU: one process per GPU (torch.distributed.run); every rank decodes its o
 batch (units partition with no data-path collective, "weak" scaling); the only
 collectives are the timing barrier and the max-over-ranks of the elapsed time.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line with the
+steps' rate (`value`, `ms_per_step`).  `--full` adds, after the timed steps and in runs of their own, everything
+else the line reports: CPU baselines (every workload), and for the default line the step spread, per-kernel and
+roofline figures, 16 half-iterations, the 8-bit decoder, the output check against the reference decoder and the
+PDSCH / PUSCH chains.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -93,6 +99,28 @@ def emit_line(result, workload):
         fe.setdefault("kernel", k)
         trace_traffic(fe, workload)
     print(json.dumps(result), flush=True)
+
+
+DUMP_BUDGET = 48 << 20  # bytes of float32 a --dump-outputs directory holds at most
+
+
+def dump_outputs(args, rank, arrays):
+    """--dump-outputs DIR (rank 0): `arrays` (name -> array with one row per unit of the batch, as the last timed
+    step left it) as DIR/<name>.npy in float32.  Above DUMP_BUDGET every array keeps the same fraction of its rows,
+    chosen by a fixed seed (the same rows in every run of the same arguments), their numbers in <name>_rows.npy."""
+    if not args.dump_outputs or rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    arrays = {k: np.asarray(v).reshape(len(v), -1) for k, v in arrays.items()}
+    total = sum(a.size * 4 for a in arrays.values())
+    rng = np.random.default_rng(0xD0)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET:
+            keep = max(1, int(len(a) * DUMP_BUDGET / total))
+            rows = np.sort(rng.choice(len(a), keep, replace=False))
+            np.save(os.path.join(args.dump_outputs, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float32))
 
 
 def shard(rank):
@@ -225,6 +253,16 @@ def parse():
                         "launcher N > 1 starts the N ranks itself")
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also everything beside the headline figure: CPU baselines, per-kernel "
+                        "and roofline figures, step spread, 16 half-iterations, the 8-bit decoder, the output check "
+                        "against the reference decoder, and the PDSCH / PUSCH chains of the default line.  Off: set "
+                        "up, warm up, time --steps steps, print the line (--cpu-seconds and the --pdsch-* legs need "
+                        "--full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (the arrays a caller of the timed path receives) as "
+                        "DIR/<name>.npy, float32; more than 48 MB of them as a fixed, seeded sample of rows "
+                        "(<name>_rows.npy: the row numbers)")
     p.add_argument("--workload", choices=["all188", "k6144", "dlsch", "ulsch", "pusch", "dlenc", "pdsch", "dlloop", "ldpc",
                                           "nrsch"],
                    default="all188")
@@ -236,7 +274,7 @@ def parse():
     p.add_argument("--sigma", type=float, default=0.42, help="dlsch: AWGN std on +-1 symbols before LLR scaling")
     p.add_argument("--batch", type=int, default=1024, help="code blocks per size per step")
     p.add_argument("--iters", type=int, default=8, help="half-iterations (srsran nof_iterations)")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget (0 = skip)")
     p.add_argument("--pool", type=int, default=8, help="distinct AWGN code blocks per size")
     p.add_argument("--bg", type=int, default=1, choices=[1, 2], help="ldpc: base graph")
     p.add_argument("--ls", type=int, default=384, help="ldpc: lifting size")
@@ -260,7 +298,7 @@ def parse():
                    help="pdsch: the workers' streams from srsran_gpu_worker_stream_create, a hardware queue each "
                         "(own), or ordinary streams on HIP's shared hardware queues (shared)")
     p.add_argument("--pdsch-steps", type=int, default=20,
-                   help="all188: timed steps of the C3 PDSCH chain reported in the same line (0 = skip)")
+                   help="all188 --full: timed steps of the C3 PDSCH chain reported in the same line (0 = skip)")
     p.add_argument("--pdsch-cpu-seconds", type=float, default=4.0, help="all188: CPU baseline budget of the PDSCH part")
     p.add_argument("--pdsch-low-snr", type=float, default=17.0,
                    help="all188: SNR (dB) of a second, shorter PDSCH chain run at the operating point where the "
@@ -544,6 +582,8 @@ def run_dlsch(args, torch, dist, world, rank, device):
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, torch.cuda.synchronize, device)
     res = d_res.cpu().numpy()
     avg = d_avg.cpu().numpy()
+    dump_outputs(args, rank, {"tb_data": d_data[:, : C3_TBS // 8].cpu().numpy(), "tb_result": res,
+                              "avg_iterations": avg})
     bits_per_step = ntb * C3_TBS
     value = world * bits_per_step * args.steps / elapsed / 1e6
 
@@ -779,6 +819,13 @@ def run_pusch(args, torch, dist, world, rank, device, steps=None, warmup=None, c
                    for w in workers for b in range(nue)])
     avg = np.array([w["res"][b].avg_iterations_block for w in workers for b in range(nue)])
     value = world * nwork * nue * C3_TBS * steps / elapsed / 1e6
+    if emit:  # each worker's last batch: payloads, CRC flags, average half-iterations
+        out = {}
+        for i, w in enumerate(workers):
+            out[f"worker{i}_tb_data"] = w["datas"][:, : C3_TBS // 8]
+            out[f"worker{i}_crc"] = np.array([bool(w["res"][b].crc) for b in range(nue)])
+            out[f"worker{i}_avg_iterations"] = np.array([w["res"][b].avg_iterations_block for b in range(nue)])
+        dump_outputs(args, rank, out)
 
     prof.enable(True)
     nrep = max(1, min(steps, 3))
@@ -920,6 +967,7 @@ def run_dlenc(args, torch, dist, world, rank, device):
     from oracle import Oracle
     ora = Oracle()
     out = d_out.cpu().numpy()
+    dump_outputs(args, rank, {"e_bits_packed": out})
     chk = [int(np.array_equal(out[i], np.packbits(ora.dlsch_encode(C3_TBS, C3_QM, 0, C3_BITS, host[i]))))
            for i in range(0, ntb, max(1, ntb // 8))]
     algo = ntb * (C3_TBS // 8 + C3_BITS // 8 + C3_BITS)  # payload in, packed e out, unpacked scratch once
@@ -1013,6 +1061,8 @@ def run_dlloop(args, torch, dist, world, rank, device):
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, torch.cuda.synchronize, device)
     ok = float((d_res == 0).float().mean().item())
     match = bool(torch.equal(d_pl[:, :, : C3_TBS // 8], d_tx_pl))
+    dump_outputs(args, rank, {"tb_data": d_pl[:, :, : C3_TBS // 8].cpu().numpy(), "tb_result": d_res.cpu().numpy(),
+                              "avg_iterations": d_avg.cpu().numpy()})
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(stream)
     for _ in range(args.steps):
@@ -1178,6 +1228,10 @@ def run_pdsch(args, torch, dist, world, rank, device, steps=None, warmup=None, c
             raise RuntimeError("srsran_ue_dl_gpu_decode_batch failed")
     torch.cuda.synchronize()
     elapsed = timed_region(step_workers, steps, warmup, world, dist, torch.cuda.synchronize, device)
+    if emit:  # the last timed step's batch, from the worker that took it
+        w = workers[(turn[0] - 1) % nwork]
+        dump_outputs(args, rank, {"tb_data": w[2][:, :, : C3_TBS // 8].cpu().numpy(), "tb_result": w[3].cpu().numpy(),
+                                  "avg_iterations": w[4].cpu().numpy()})
     if getattr(args, "pdsch_probe", False):
         pdsch_probe(step, steps, torch, device, prof)
     # PCIe-inclusive rate (never `value`): every step's time samples start in pinned host memory.
@@ -1504,6 +1558,7 @@ def run_ldpc(args, torch, dist, world, rank, device):
 
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, torch.cuda.synchronize, device)
     value = world * ncw * liftK * args.steps / elapsed / 1e6
+    dump_outputs(args, rank, {"message_bits_packed": d_out.cpu().numpy()})
     ms = []
     for _ in range(max(1, min(args.steps, 3))):
         e0 = torch.cuda.Event(enable_timing=True)
@@ -1634,6 +1689,7 @@ def run_nrsch(args, torch, dist, world, rank, device):
     avg = d_avg.cpu().numpy()
     out = d_p.cpu().numpy()
     payload_ok = all(np.array_equal(out[i, :tbs // 8], pays[i % args.pool]) for i in range(ntb) if crc[i])
+    dump_outputs(args, rank, {"tb_data": out[:, : tbs // 8], "crc": crc, "avg_iterations": avg})
 
     prof.enable(True)
     nrep = max(1, min(args.steps, 3))
@@ -1804,6 +1860,8 @@ def main():
     world = world or 1
     if args.dry_run:
         return dry_run(args)
+    if not args.full:
+        args.cpu_seconds = 0  # CPU baselines, of every workload, belong to --full
     import torch
     import torch.distributed as dist
 
@@ -1873,6 +1931,49 @@ def main():
 
     bits_per_step = args.batch * sum(Ks)
     value = world * bits_per_step * args.steps / elapsed / 1e6
+    if args.dump_outputs:
+        # every block the last timed step decoded: one row a batch index, the sizes' K / 8 bytes side by side
+        dump_outputs(args, rank, {"decoded_bytes": np.concatenate([data[K][1].cpu().numpy() for K in Ks], axis=1)})
+
+    base = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "Mbps",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int16",
+        "data": "synthetic: AWGN turbo code blocks (Eb/No label 4 dB, turbodecoder_test.c convention), "
+                f"{args.pool} distinct blocks per size tiled to the batch, HBM-resident",
+        "config": {
+            "workload": ("tdec all 188 LTE CB sizes x %d CBs, %d half-its, rm_turbo SB layout" % (args.batch, args.iters))
+            if args.workload == "all188" else ("tdec K=6144 x %d CBs, %d half-its, rm_turbo SB layout" % (args.batch, args.iters)),
+            "cbs_per_size": args.batch,
+            "cb_sizes": len(Ks),
+            "half_iterations": args.iters,
+            "info_bits_per_step_per_gpu": bits_per_step,
+            "parallelism": f"cb-sharded x{world}",
+            "tdec16": args.tdec16,
+        },
+        "full": bool(args.full),
+    }
+    # a plain run ends here: the line above is all its headline figure needs
+    result = tdec_full_line(args, torch, dist, world, rank, device, tdec, base, Ks, data, groups, step, stream, sp,
+                            bits_per_step) if args.full else base
+    if world > 1:
+        dist.destroy_process_group()
+    if rank == 0:
+        emit_line(result, args.workload)
+
+
+def tdec_full_line(args, torch, dist, world, rank, device, tdec, base, Ks, data, groups, step, stream, sp, bits_per_step):
+    """--full, all188 / k6144: what the line reports beside the timed steps' rate (`base`), each in runs of its own
+    after the timed region: step spread, per-kernel and roofline figures, 16 half-iterations, the output check
+    against the reference decoder, the 8-bit decoder, the CPU baselines and (all188) the PDSCH / PUSCH chains."""
     spread = step_spread(step, max(args.steps, 5), torch, stream)
 
     # ---- per-launch kernel durations (HIP events on the launch stream), outside the timed region ----
@@ -1967,30 +2068,7 @@ def main():
         exp = want[K][np.arange(args.batch) % args.pool]
         bad += int((got != exp).any(axis=1).sum())
 
-    result = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "Mbps",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int16",
-        "data": "synthetic: AWGN turbo code blocks (Eb/No label 4 dB, turbodecoder_test.c convention), "
-                f"{args.pool} distinct blocks per size tiled to the batch, HBM-resident",
-        "config": {
-            "workload": ("tdec all 188 LTE CB sizes x %d CBs, %d half-its, rm_turbo SB layout" % (args.batch, args.iters))
-            if args.workload == "all188" else ("tdec K=6144 x %d CBs, %d half-its, rm_turbo SB layout" % (args.batch, args.iters)),
-            "cbs_per_size": args.batch,
-            "cb_sizes": len(Ks),
-            "half_iterations": args.iters,
-            "info_bits_per_step_per_gpu": bits_per_step,
-            "parallelism": f"cb-sharded x{world}",
-            "tdec16": args.tdec16,
-        },
+    result = dict(base, **{
         "roofline": dict({
             "bound": "hbm",
             "kernel": dom,
@@ -2007,7 +2085,7 @@ def main():
         "mbps_16_half_its": round(mbps_16, 1),
         "output_check": {"blocks": args.batch * len(Ks), "mismatched": bad,
                          "against": "reference decoder (oracle/_ref) on each pool block"},
-    }
+    })
     if args.workload == "all188":
         k = [e for e in events if e[0] == 6144]
         if k:
@@ -2036,7 +2114,7 @@ def main():
 
     if args.workload == "all188" and args.pdsch_steps > 0:
         # the PDSCH half of the metric (BASELINE configs[2], C3): the whole UE DL chain, same line
-        del data
+        data.clear()  # the caller's dict too: the turbo batch leaves the device
         torch.cuda.empty_cache()
         pd = run_pdsch(args, torch, dist, world, rank, device, steps=args.pdsch_steps, warmup=3,
                        cpu_seconds=args.pdsch_cpu_seconds if args.cpu_seconds > 0 else 0, emit=False)
@@ -2095,11 +2173,7 @@ def main():
             "batch_workers": pu["config"]["batch_workers"],
             "cpu_baseline": pu.get("cpu_baseline"),
         }
-
-    if world > 1:
-        dist.destroy_process_group()
-    if rank == 0:
-        emit_line(result, args.workload)
+    return result
 
 
 if __name__ == "__main__":

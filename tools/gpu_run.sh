@@ -6,7 +6,8 @@
 #   tests[:PYTEST_SELECTION]   pytest -m gpu (default: tests), e.g. tests:tests/test_pusch_gpu.py
 #   testse:ENV:SELECTION       the same with ENV (VAR=VAL[,VAR=VAL]) in the environment
 #   smoke                      __graft_entry__.smoke()
-#   bench:NAME[:ARGS]          python bench.py ARGS > bench_NAME.json (ARGS space-separated, e.g. "--steps 10")
+#   bench:NAME[:ARGS]          python bench.py ARGS > bench_NAME.json (ARGS space-separated, e.g. "--full --steps 10";
+#                              without --full the line and its digest hold the timed steps' rate alone)
 #   benche:NAME:ENV:ARGS       the same with ENV (VAR=VAL[,VAR=VAL]) in the environment
 #   prof:NAME[:ARGS]           rocprofv3 --kernel-trace --stats of bench.py ARGS -> prof_NAME/
 #   pmc:NAME[:ARGS]            tools/pmc_tdec.sh passes over tools/tdec_kernels.py ARGS -> NAME/

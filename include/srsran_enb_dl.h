@@ -12,7 +12,10 @@
  *     srsran_dlsch_encode2, srsran_sequence_pdsch_apply_pack, srsran_mod_modulate_bytes,
  *     srsran_layermap_type / srsran_precoding_type, srsran_pdsch_put),
  *   srsran_enb_dl_gen_signal (enb_dl.c:446-470: amplitude 0.05 / sqrt(N_RB), srsran_ofdm_tx_sf).
- * Transmission schemes: PORT0 (1 port), TX diversity (2 or 4 ports, 1 TB), CDD (2 ports, 2 TBs); normal or
+ * Transmission schemes: PORT0 (1 port), TX diversity (2 or 4 ports, 1 TB), CDD (2 ports, 2 TBs), closed-loop
+ * spatial multiplexing (2 ports, srsran_precoding_multiplex, precoding.c:2087-2211: 1 layer / 1 TB with codebooks
+ * 0..3, 2 layers / 2 TBs or 1 TB with codebooks 0..2; codebook = pmi with one TB, pmi + 1 with two; one TB on two
+ * layers carries 2 x the PDSCH REs modulation symbols, even ones on layer 0, odd ones on layer 1); normal or
  * extended CP;
  * rho_a = 1.  Not generated here (their REs stay empty): PHICH, MBSFN subframes.
  */
@@ -53,7 +56,8 @@ int  srsran_enb_dl_gpu_init(srsran_enb_dl_gpu_t* q, srsran_cell_t cell);
 void srsran_enb_dl_gpu_free(srsran_enb_dl_gpu_t* q);
 /* nof_sf subframes -> d_samples [nof_sf][cell.nof_ports][SRSRAN_SF_LEN(symbol_sz)] (device), the grid
  * scaled by `scale` before the modulator (scale <= 0: the reference's 0.05 / sqrt(N_RB)); every TB's
- * nof_bits must equal the grant's PDSCH REs x Qm (x 2 for transmit diversity's codeword).
+ * nof_bits must equal the grant's PDSCH REs x Qm (x 2 for transmit diversity's codeword; x nof_layers /
+ * nof_tb with spatial multiplexing).
  * Asynchronous on `stream` after the host has built the RE tables. */
 int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
                                uint32_t                      nof_sf,

@@ -300,7 +300,8 @@ int srsran_pdsch_re_table(const srsran_cell_t*        cell,
  * through the srsran_pdsch_re_table order), rho_b scaling of CRS symbols fused there too,
  * demapping + descrambling + CSI correction fused into one LLR kernel, then DL-SCH decode.
  * Provided: PORT0 (1 port), TX diversity (2 or 4 ports, 1 codeword; layer demap fused), CDD and
- * SPATIALMUX (2 ports x 2 rx, 1 or 2 codewords on 2 layers), MMSE (ZF = MMSE with noise 0, as
+ * SPATIALMUX (2 ports x 2 rx, 1 or 2 codewords on 2 layers; one codeword on one layer with codebooks 0..3,
+ * srsran_predecoding_multiplex_2x1_mrc_csi over both rx antennas), MMSE (ZF = MMSE with noise 0, as
  * pdsch.c:811 passes it), 16- and 8-bit LLRs (llr_is_8bit), EVM (meas_evm_en), normal and extended CP, FDD and
  * TDD cells (DwPTS grants of special subframes).
  * Not provided (SRSRAN_ERROR): 4-port CDD / SM (refused by the reference too), MBSFN subframes (the PMCH).
@@ -328,8 +329,10 @@ typedef struct {
 int  srsran_pdsch_init_ue(srsran_pdsch_t* q, uint32_t max_prb, uint32_t nof_rx_antennas);
 /* eNB side (pdsch.c:302-310, 1015-1120): srsran_pdsch_encode writes the PDSCH REs of the ports'
  * host grids (the rest is left as the caller put it: CRS, control channels).  PORT0 (1 port), TX
- * diversity (2 ports, 1 TB), CDD (2 ports, 2 TBs); rho_a scaling (power_scale with p_a != 0) is not
- * provided.  Runs on the GPU: DL-SCH encoding, scrambling, modulation, precoding, RE mapping. */
+ * diversity (2 ports, 1 TB), CDD (2 ports, 2 TBs), SPATIALMUX (2 ports: 1 layer / 1 TB with codebooks 0..3,
+ * 2 layers / 2 TBs or 1 TB with codebooks 0..2, srsran_enb_dl.h); rho_a scaling (power_scale with p_a != 0) is not
+ * provided.  Not provided (SRSRAN_ERROR): 4-port CDD / SM and two-layer codebook 3, which the reference's precoder
+ * refuses too (precoding.c:2196-2209).  Runs on the GPU: DL-SCH encoding, scrambling, modulation, precoding, RE mapping. */
 int  srsran_pdsch_init_enb(srsran_pdsch_t* q, uint32_t max_prb);
 int  srsran_pdsch_encode(srsran_pdsch_t*     q,
                          srsran_dl_sf_cfg_t* sf,
@@ -390,7 +393,9 @@ int srsran_pdsch_gpu_last_evm(srsran_pdsch_t* q, uint32_t sf, uint32_t tb, const
  * fft_mbsfn transforms antenna 0's input buffer into sf_symbols[0] and the other antennas' grids keep the
  * previous subframe, as in the reference (ue_dl.c:104-111, 353-356, 373-376); then the MBSFN estimator and the
  * PCFICH / PDCCH of the non-MBSFN region.  srsran_ue_dl_find_dl_dci / srsran_ue_dl_dci_to_pdsch_grant are in
- * srsran_pdcch.h.  PHICH / PMCH are not provided.  srsran_dl_cfg_t omits the reference's leading cqi_report. */
+ * srsran_pdcch.h.  PHICH / PMCH are not provided.  srsran_dl_cfg_t omits the reference's leading cqi_report, so
+ * srsran_ue_dl_gen_cqi_periodic / _aperiodic are not provided either; the feedback they report (RI, PMI, SINR) is:
+ * section "channel-state feedback" at the end of this header. */
 typedef enum { SRSRAN_TM1 = 0, SRSRAN_TM2, SRSRAN_TM3, SRSRAN_TM4, SRSRAN_TM5, SRSRAN_TM6, SRSRAN_TM7, SRSRAN_TM8,
                SRSRAN_TMINV } srsran_tm_t;
 
@@ -504,6 +509,87 @@ int  srsran_cfo_resize(srsran_cfo_t* h, uint32_t samples);
 void srsran_cfo_set_tol(srsran_cfo_t* h, float tol);
 /* output[n] = input[n] * exp(j 2 pi freq n), n = 0..nsamples-1 */
 void srsran_cfo_correct(srsran_cfo_t* h, const cf_t* input, cf_t* output, float freq);
+
+/* ---------------- channel-state feedback: RI / PMI / SINR (mimo/precoding.h, pdsch.c:1143-1167, ue_dl.c:750-843,
+ * cqi.c:740-748) ----------------
+ * One HIP reduction over the channel estimate of a 2-port x 2-rx cell (csi_kernel.hip), one workgroup a subframe:
+ * the SINR of every closed-loop codebook entry on the sample set of the reference's AVX2 release build
+ * (srsran_precoding_pmi_select_1l_simd / _2l_simd: indices 192 b + 24 k, k < 8, of every whole block b of 192, with
+ * float division where that code uses rcp), the condition number over every 24th index (srsran_precoding_2x2_cn_gen,
+ * srsran_mat_2x2_cn), and the decisions the reference's callers take from them.
+ * srsran_ue_dl_gen_cqi_periodic / _aperiodic are not provided: they read cqi_report of srsran_dl_cfg_t, which this
+ * project's struct omits (above); adding it is a layout change.  A caller builds its report from
+ * srsran_ue_dl_select_ri / srsran_ue_dl_select_ri_pmi and srsran_cqi_from_snr. */
+#ifndef SRSRAN_MAX_CODEBOOKS
+#define SRSRAN_MAX_CODEBOOKS 4
+#endif
+#ifndef SRSRAN_NOF_RE
+#define SRSRAN_NOF_RE(cell) SRSRAN_SF_LEN_RE((cell).nof_prb, (cell).cp)
+#endif
+
+/* added: the feedback of one subframe (64 bytes) */
+typedef struct {
+  float    sinr_1l[4];  /* linear SINR of the one-layer precoders [1, q] / sqrt 2, q = +1, -1, +j, -j */
+  float    sinr_2l[2];  /* linear SINR (both layers' gammas summed) of the two-layer codebooks 0 and 1 */
+  float    cn;          /* condition number in dB, averaged over the samples counted */
+  float    sinr_db;     /* select_ri_pmi's SINR in dB of the (ri, pmi) below */
+  uint32_t pmi_1l;      /* first strict maximum of sinr_1l, from 0 */
+  uint32_t pmi_2l;      /* first strict maximum of sinr_2l, from 0 */
+  uint32_t ri_cn;       /* srsran_ue_dl_select_ri's rank indicator: cn < 17 (TM3) */
+  uint32_t ri;          /* select_ri_pmi's (ue_dl.c:778-822, TM4): 1 (two layers) if the two-layer SINR in dB exceeds */
+  uint32_t pmi;         /* the one-layer one by 0.1 or is above 20; pmi is that rank's */
+  uint32_t cn_count;    /* samples in cn (one whose eigenvalues are NaN / Inf is skipped, mat.c:146-149) */
+  uint32_t reserved[2];
+} srsran_csi_gpu_t;
+
+/* precoding.c:2771-2795 on host pointers h[port][rx] (upload, kernel, 64-byte readback): sinr[0..3] (nof_layers 1)
+ * or sinr[0..1] (2), *pmi the best one where an SINR is above 0.  Returns the number of codebook entries, or
+ * SRSRAN_ERROR_INVALID_INPUTS for another layer count and for nof_symbols < 192, where the reference's unsigned loop
+ * bound underflows and it reads past its arrays.  The noise bound of precoding.c:2781-2783 applies. */
+int srsran_precoding_pmi_select(cf_t*     h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                                uint32_t  nof_symbols,
+                                float     noise_estimate,
+                                int       nof_layers,
+                                uint32_t* pmi,
+                                float     sinr[SRSRAN_MAX_CODEBOOKS]);
+/* precoding.c:2826-2841: the condition number in dB; SRSRAN_ERROR for anything but 2 x 2, as the reference */
+int srsran_precoding_cn(cf_t*    h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                        uint32_t nof_tx_antennas,
+                        uint32_t nof_rx_antennas,
+                        uint32_t nof_symbols,
+                        float*   cn);
+/* added: the whole record of host estimates h[port][rx] of a 2 x 2 channel in one call (one upload, one kernel):
+ * what the two calls above return piece by piece, and the decisions.  nof_symbols < 192: the SINRs are 1e9, as the
+ * reference's loops leave them without a whole block (precoding.c:2446-2450). */
+int srsran_precoding_csi_2x2(cf_t*             h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                             uint32_t          nof_symbols,
+                             float             noise_estimate,
+                             srsran_csi_gpu_t* csi);
+/* pdsch.c:1143-1167 on channel->ce (host, full estimates) and channel->noise_estimate */
+int srsran_pdsch_select_pmi(srsran_pdsch_t*        q,
+                            srsran_chest_dl_res_t* channel,
+                            uint32_t               nof_layers,
+                            uint32_t*              best_pmi,
+                            float                  sinr[SRSRAN_MAX_CODEBOOKS]);
+int srsran_pdsch_compute_cn(srsran_pdsch_t* q, srsran_chest_dl_res_t* channel, float* cn);
+/* ue_dl.c:825-843 (TM3) and, added, select_ri_pmi (ue_dl.c:778-822, TM4; static in the reference, which reaches it
+ * through its CQI generators).  Both read the device estimate the last srsran_ue_dl_decode_fft_estimate(_noguru) left
+ * (no upload) and q->chest_res.noise_estimate.  cell.nof_ports < 2: SRSRAN_SUCCESS, nothing written; any other shape
+ * than 2 ports x 2 rx antennas: SRSRAN_ERROR. */
+int srsran_ue_dl_select_ri(srsran_ue_dl_t* q, uint32_t* ri, float* cn);
+int srsran_ue_dl_select_ri_pmi(srsran_ue_dl_t* q, uint32_t* ri, uint32_t* pmi, float* sinr_db);
+/* added: the feedback of every subframe of the last srsran_ue_dl_gpu_decode_batch(_sc16) on q, from the estimates and
+ * noise estimates that batch left on the device; these are valid until the next batch on q, so call this before it.
+ * d_csi: nof_sf records on the device (nof_sf <= the batch's).  Asynchronous on `stream`, ordered after the batch
+ * whatever stream that ran on. */
+int srsran_ue_dl_gpu_csi_batch(srsran_ue_dl_t* q, uint32_t nof_sf, srsran_csi_gpu_t* d_csi, void* stream);
+/* added (tests / diagnostics): what srsran_ue_dl_gpu_csi_batch reads for subframe `sf` of the last batch on q: the
+ * device estimate, nof_ports x nof_rx rows [port][rx] of *row_len cf_t each (12 nof_prb: the one-row AVERAGE form,
+ * read at index j modulo the row; SRSRAN_NOF_RE: a full one), and the device noise estimate.  Valid until the next
+ * batch on q, complete once that batch's stream has reached them. */
+int srsran_ue_dl_gpu_last_ce(srsran_ue_dl_t* q, uint32_t sf, const cf_t** d_ce, uint32_t* row_len, const float** d_noise);
+/* cqi.c:740-748: wideband CQI 0..15 of an SNR in dB (host only) */
+uint8_t srsran_cqi_from_snr(float snr);
 
 #ifdef __cplusplus
 }

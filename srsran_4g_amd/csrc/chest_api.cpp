@@ -1021,4 +1021,9 @@ int chest_dl_gpu_estimate_batch_inline(srsran_chest_dl_t*           q,
   return estimate_batch(q, cfg, nullptr, h_sf, jobs, nsf, d_grid, grid_sf_stride, d_ce, ce_sf_stride, full_grid, d_res,
                         stream);
 }
+
+const float2* chest_dl_gpu_last_ce(const srsran_chest_dl_t* q)
+{
+  return q && q->gpu ? ((const ChestGpu*)q->gpu)->ce : nullptr;
+}
 }  // namespace srsran_amd

@@ -1,0 +1,209 @@
+// srsran_4g_amd/csrc/csi_api.cpp -- channel-state feedback on host pointers (include/srsran_ue_dl.h, section
+// "channel-state feedback"): srsran_precoding_pmi_select / srsran_precoding_cn (precoding.c:2771-2841),
+// srsran_pdsch_select_pmi / srsran_pdsch_compute_cn (pdsch.c:1143-1167), srsran_cqi_from_snr (cqi.c:740-748).
+// The numbers come from csi_kernel.hip, the same kernel the device-resident forms (ue_dl_api.cpp) launch.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+#include <mutex>
+
+#include "../../include/srsran_ue_dl.h"
+#include "csi_kernel.h"
+#include "pdsch_internal.h"
+
+using namespace srsran_amd;
+
+namespace {
+
+// scratch of the host-pointer calls: four estimate rows and one record, kept for the process
+struct CsiScratch {
+  std::mutex        mu;
+  float2*           d_h   = nullptr;
+  size_t            cap   = 0;  // float2 a row
+  srsran_csi_gpu_t* d_out = nullptr;
+};
+CsiScratch& scratch()
+{
+  static CsiScratch s;
+  return s;
+}
+
+// the record of one subframe; d_ce == nullptr: the host rows h[port][rx] are uploaded first
+int csi_run(const float2* d_ce, cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS], size_t row_stride, uint32_t row_len,
+            uint32_t nof_symbols, float noise, srsran_csi_gpu_t* out)
+{
+  CsiScratch&                 s = scratch();
+  std::lock_guard<std::mutex> lock(s.mu);
+  if (!s.d_out && hipMalloc((void**)&s.d_out, sizeof(srsran_csi_gpu_t)) != hipSuccess) {
+    s.d_out = nullptr;
+    return SRSRAN_ERROR;
+  }
+  if (!d_ce) {
+    if (nof_symbols > s.cap) {
+      hipFree(s.d_h);
+      s.d_h = nullptr;
+      s.cap = 0;
+      if (hipMalloc((void**)&s.d_h, 4 * (size_t)nof_symbols * sizeof(float2)) != hipSuccess) {
+        s.d_h = nullptr;
+        return SRSRAN_ERROR;
+      }
+      s.cap = nof_symbols;
+    }
+    for (uint32_t p = 0; p < 2; p++) {
+      for (uint32_t r = 0; r < 2; r++) {
+        if (hipMemcpyAsync(s.d_h + (2 * p + r) * s.cap, h[p][r], (size_t)nof_symbols * sizeof(cf_t),
+                           hipMemcpyHostToDevice, nullptr) != hipSuccess) {
+          return SRSRAN_ERROR;
+        }
+      }
+    }
+    d_ce       = s.d_h;
+    row_stride = s.cap;
+    row_len    = nof_symbols;
+  }
+  CsiArgs a{};
+  a.ce          = d_ce;
+  a.sf_stride   = 0;
+  a.row_stride  = row_stride;
+  a.row_len     = row_len;
+  a.nof_symbols = nof_symbols;
+  a.noise       = nullptr;
+  a.noise_val   = noise;
+  a.out         = s.d_out;
+  if (csi_launch(a, 1, nullptr) != hipSuccess ||
+      hipMemcpyAsync(out, s.d_out, sizeof(*out), hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+bool rows_2x2(cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS])
+{
+  return h && h[0][0] && h[0][1] && h[1][0] && h[1][1];
+}
+
+}  // namespace
+
+namespace srsran_amd {
+int csi_from_device(const float2* d_ce, size_t row_stride, uint32_t row_len, uint32_t nof_symbols, float noise,
+                    srsran_csi_gpu_t* out)
+{
+  if (!d_ce || !out || row_len == 0 || nof_symbols == 0) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return csi_run(d_ce, nullptr, row_stride, row_len, nof_symbols, noise, out);
+}
+}  // namespace srsran_amd
+
+extern "C" {
+
+int srsran_precoding_pmi_select(cf_t*     h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                                uint32_t  nof_symbols,
+                                float     noise_estimate,
+                                int       nof_layers,
+                                uint32_t* pmi,
+                                float     sinr[SRSRAN_MAX_CODEBOOKS])
+{
+  if (nof_layers != 1 && nof_layers != 2) {
+    fprintf(stderr, "[srsran_precoding] Unsupported number of layers\n");
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (!rows_2x2(h) || nof_symbols < 192) {  // 192: one block of the SIMD sample set
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  srsran_csi_gpu_t o;
+  if (csi_run(nullptr, h, 0, 0, nof_symbols, noise_estimate, &o) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR;
+  }
+  const uint32_t n = nof_layers == 1 ? 4 : 2, best = nof_layers == 1 ? o.pmi_1l : o.pmi_2l;
+  const float*   v = nof_layers == 1 ? o.sinr_1l : o.sinr_2l;
+  for (uint32_t i = 0; i < n && sinr; i++) {
+    sinr[i] = v[i];
+  }
+  if (pmi && v[best] > 0.0f) {  // the reference writes *pmi only where an SINR exceeds its starting maximum of 0
+    *pmi = best;
+  }
+  return (int)n;
+}
+
+int srsran_precoding_cn(cf_t*    h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                        uint32_t nof_tx_antennas,
+                        uint32_t nof_rx_antennas,
+                        uint32_t nof_symbols,
+                        float*   cn)
+{
+  if (nof_tx_antennas != 2 || nof_rx_antennas != 2) {
+    fprintf(stderr, "[srsran_precoding] MIMO Condition Number calculation not implemented for %ux%u\n", nof_tx_antennas,
+            nof_rx_antennas);
+    return SRSRAN_ERROR;
+  }
+  if (!rows_2x2(h) || !cn || nof_symbols == 0) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  srsran_csi_gpu_t o;
+  if (csi_run(nullptr, h, 0, 0, nof_symbols, 0.0f, &o) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR;
+  }
+  *cn = o.cn;
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_precoding_csi_2x2(cf_t*             h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS],
+                             uint32_t          nof_symbols,
+                             float             noise_estimate,
+                             srsran_csi_gpu_t* csi)
+{
+  if (!rows_2x2(h) || !csi || nof_symbols == 0) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return csi_run(nullptr, h, 0, 0, nof_symbols, noise_estimate, csi);
+}
+
+int srsran_pdsch_select_pmi(srsran_pdsch_t*        q,
+                            srsran_chest_dl_res_t* channel,
+                            uint32_t               nof_layers,
+                            uint32_t*              best_pmi,
+                            float                  sinr[SRSRAN_MAX_CODEBOOKS])
+{
+  if (!q || !channel) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (q->cell.nof_ports != 2 || q->nof_rx_antennas != 2) {
+    fprintf(stderr, "[srsran_pdsch] PMI selection: 2 ports x 2 rx antennas only (%u x %u)\n", q->cell.nof_ports,
+            q->nof_rx_antennas);
+    return SRSRAN_ERROR;
+  }
+  uint32_t pmi = 0;
+  if (srsran_precoding_pmi_select(channel->ce, SRSRAN_NOF_RE(q->cell), channel->noise_estimate, (int)nof_layers, &pmi,
+                                  sinr) < 0) {
+    fprintf(stderr, "[srsran_pdsch] PMI Select for %u layers\n", nof_layers);
+    return SRSRAN_ERROR;
+  }
+  if (best_pmi) {
+    *best_pmi = pmi;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_pdsch_compute_cn(srsran_pdsch_t* q, srsran_chest_dl_res_t* channel, float* cn)
+{
+  if (!q || !channel) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return srsran_precoding_cn(channel->ce, q->cell.nof_ports, q->nof_rx_antennas, SRSRAN_NOF_RE(q->cell), cn);
+}
+
+uint8_t srsran_cqi_from_snr(float snr)
+{
+  // "Downlink SNR to CQI Mapping for Different Multiple Antenna Techniques in LTE", Table III (cqi.c:735)
+  static const float kCqiToSnr[15] = {1.95, 4, 6, 8, 10, 11.95, 14.05, 16, 17.9, 20.9, 22.5, 24.75, 25.5, 27.30, 29};
+  for (int cqi = 14; cqi >= 0; cqi--) {
+    if (snr >= kCqiToSnr[cqi]) {
+      return (uint8_t)(cqi + 1);
+    }
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -389,6 +389,9 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
       scheme = 4;
     } else if (gr.tx_scheme == SRSRAN_TXSCHEME_CDD && P == 2 && gr.nof_tb == 2 && gr.nof_layers == 2) {
       scheme = 3;
+    } else if (gr.tx_scheme == SRSRAN_TXSCHEME_SPATIALMUX &&
+               pdsch_tx_sm_ok(P, gr.nof_layers, gr.nof_tb, gr.nof_tb == 1 ? gr.pmi : gr.pmi + 1)) {
+      scheme = 2;
     } else {
       fprintf(stderr, "[srsran_enb_dl] transmission scheme %d with %u ports / %u TBs is not provided\n",
               (int)gr.tx_scheme, P, gr.nof_tb);
@@ -409,6 +412,12 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
     // scaling * M_SQRT1_2 (2 ports); scaling /= M_SQRT2 (4 ports, precoding.c:1962)
     it.div_scale = scheme == 4 ? (float)(it.scaling / 1.41421356237309504880)
                                : (float)((double)it.scaling * 0.70710678118654752440);
+    if (scheme == 2) {
+      it.nl        = gr.nof_layers;
+      it.ncw       = gr.nof_tb;
+      it.cb        = gr.nof_tb == 1 ? gr.pmi : gr.pmi + 1;
+      it.div_scale = pdsch_tx_sm_scale(it.scaling, it.nl, it.cb);
+    }
     uint32_t cw = 0;
     for (uint32_t t = 0; t < SRSRAN_MAX_CODEWORDS; t++) {
       const srsran_ra_tb_t& tb = gr.tb[t];
@@ -416,7 +425,9 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
         continue;
       }
       const uint32_t Qm = srsran_mod_bits_x_symbol(tb.mod), Nl = gr.nof_layers != gr.nof_tb ? 2 : 1;
-      if (!s.d_data[t] || Qm == 0 || tb.nof_bits != nre * Qm || tb.tbs <= 0 || cw >= 2) {
+      // SM: a codeword fills nof_layers / nof_tb layers of nre symbols each
+      const uint32_t lpc = scheme == 2 ? gr.nof_layers / gr.nof_tb : 1;
+      if (!s.d_data[t] || Qm == 0 || tb.nof_bits != nre * Qm * lpc || tb.tbs <= 0 || cw >= 2) {
         fprintf(stderr, "[srsran_enb_dl] TB %u: nof_bits %u does not match %u REs x Qm %u\n", t, tb.nof_bits, nre, Qm);
         return SRSRAN_ERROR_INVALID_INPUTS;
       }
@@ -427,7 +438,7 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
       e_tot += ((tb.nof_bits + 7) / 8 + 15) & ~(size_t)15;
       cw++;
     }
-    if ((scheme == 3) != (cw == 2)) {
+    if (cw != (scheme == 3 ? 2u : scheme == 2 ? gr.nof_tb : 1u)) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
     pd_sf.push_back(b);
@@ -448,7 +459,7 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
     for (uint32_t p = 0; p < P; p++) {
       it.grid[p] = g->d_grid + ((size_t)b * P + p) * nre_sf;
     }
-    const uint32_t ncw = it.scheme == 3 ? 2 : 1;
+    const uint32_t ncw = it.scheme == 3 ? 2 : it.scheme == 2 ? it.ncw : 1;
     for (uint32_t c = 0; c < ncw; c++, k++) {
       enc[k].d_e_bits = g->d_e + e_off[k];
       it.e[c]         = g->d_e + e_off[k];

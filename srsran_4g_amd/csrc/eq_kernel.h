@@ -13,7 +13,7 @@ struct PredArgs {
   float*        csi[2];   // [layer] CSI (srsran_predecoding_*_csi)
   uint32_t*     csi_max;  // optional [layer] running max of csi (float bits, csi >= 0)
   int           scheme;   // 0 PORT0, 1 DIVERSITY (n = REs, n/2 pairs), 2 SPATIALMUX, 3 CDD, 4 DIVERSITY on 4 ports
-                          // (n/4 SFBC + FSTD groups)
+                          // (n/4 SFBC + FSTD groups), 5 SPATIALMUX with one layer (2 ports x 2 rx, codebook 0..3)
   int           nrx;
   int           codebook;
   uint32_t      n;

@@ -304,6 +304,28 @@ __device__ __forceinline__ void predecode_item(const PredArgs& a, uint32_t k, ui
     if (valid) {
       mx[0] = max(mx[0], __float_as_uint(csi));
     }
+  } else if constexpr (SCHEME == 5) {
+    // srsran_predecoding_multiplex_2x1_mrc_csi (precoding.c:1727-1812, its scalar form with float division): one
+    // layer on 2 ports, maximum-ratio combining of both rx antennas over h = h[0][rx] + {1, -1, j, -j} h[1][rx];
+    // a.norm = M_SQRT2 / scaling
+    cpx   r  = {0.f, 0.f};
+    float hh = 0.f;
+    for (int p = 0; p < 2; p++) {
+      const cpx h0 = ld(a.h[0][p], gh), h1 = ld(a.h[1][p], gh);
+      const cpx hx = a.codebook == 0   ? cadd(h0, h1)
+                     : a.codebook == 1 ? csub(h0, h1)
+                     : a.codebook == 2 ? cadd(h0, cmulj(h1))
+                                       : csub(h0, cmulj(h1));
+      r            = cadd(r, cmul(cconj(hx), Y(p)));
+      hh += hx.r * hx.r + hx.i * hx.i;
+    }
+    const float s   = a.norm / hh;
+    const float csi = hh / a.norm * (float)0.70710678118654752440;
+    if (valid) {
+      a.csi[0][k] = csi;
+      a.x[0][k]   = make_float2(r.r * s, r.i * s);
+      mx[0]       = max(mx[0], __float_as_uint(csi));
+    }
   } else {
     const cpx p0 = ld(a.h[0][0], gh), p1 = ld(a.h[0][1], gh), q0 = ld(a.h[1][0], gh), q1 = ld(a.h[1][1], gh);
     cpx       h00, h01, h10, h11;
@@ -482,7 +504,7 @@ __device__ __forceinline__ void predecode_block(const PredArgs& a, uint32_t k0)
     }
   }
   if (a.csi_max) {
-    if constexpr (SCHEME == 0 || SCHEME == 1 || SCHEME == 4) {
+    if constexpr (SCHEME == 0 || SCHEME == 1 || SCHEME == 4 || SCHEME == 5) {
       const uint32_t m1[1] = {mx[0]};
       block_max_atomic<1>(a.csi_max, m1, red);
     } else {
@@ -560,6 +582,9 @@ hipError_t predecode_batch_launch(const PredArgs* d_items, uint32_t nitems, int 
     case 4:
       hipLaunchKernelGGL(predecode_batch_kernel<4>, grid, dim3(EQ_THREADS), 0, stream, d_items);
       break;
+    case 5:
+      hipLaunchKernelGGL(predecode_batch_kernel<5>, grid, dim3(EQ_THREADS), 0, stream, d_items);
+      break;
     default:
       return hipErrorInvalidValue;
   }
@@ -592,6 +617,9 @@ hipError_t predecode_launch(const PredArgs& a, hipStream_t stream)
       break;
     case 4:
       hipLaunchKernelGGL(predecode_kernel<4>, grid, dim3(EQ_THREADS), 0, stream, a);
+      break;
+    case 5:
+      hipLaunchKernelGGL(predecode_kernel<5>, grid, dim3(EQ_THREADS), 0, stream, a);
       break;
     default:
       return hipErrorInvalidValue;

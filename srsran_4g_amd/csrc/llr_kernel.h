@@ -80,10 +80,26 @@ struct PdschTx {
   float2*         grid[4];  // per-port subframe grids (2 nsymb x 12 nof_prb)
   uint32_t        nre;      // PDSCH REs
   int             scheme;   // 0: one port; 1: transmit diversity (2 ports, 1 codeword); 3: CDD 2x2 (2 codewords);
-                            // 4: transmit diversity on 4 ports (SFBC + FSTD, 1 codeword)
+                            // 4: transmit diversity on 4 ports (SFBC + FSTD, 1 codeword);
+                            // 2: spatial multiplexing on 2 ports (nl layers, codebook cb; 1 or 2 codewords)
   float           scaling;  // rho_a scaling of the precoder (1)
-  float           div_scale;// (float)(scaling * M_SQRT1_2) for 2-port, (float)(scaling / M_SQRT2) for 4-port diversity
+  float           div_scale;// (float)(scaling * M_SQRT1_2) for 2-port, (float)(scaling / M_SQRT2) for 4-port diversity;
+                            // scheme 2: pdsch_tx_sm_scale
+  uint32_t        nl;       // scheme 2: layers (1, 2)
+  uint32_t        cb;       // scheme 2: codebook index (pmi with one codeword, pmi + 1 with two)
+  uint32_t        ncw;      // scheme 2: codewords (1, 2); one codeword on two layers is split even / odd
 };
+// Spatial multiplexing on 2 ports (scheme 2): whether the reference precodes (layers, codewords, codebook)
+// (precoding.c:2087-2211; two-layer codebook 3 is refused there), and the factor it multiplies with, in its
+// order of operations: scaling *= M_SQRT1_2 (one layer, two layers codebook 0) or scaling /= 2.0f.
+inline bool pdsch_tx_sm_ok(uint32_t P, uint32_t nl, uint32_t ntb, uint32_t cb)
+{
+  return P == 2 && ((nl == 1 && ntb == 1 && cb < 4) || (nl == 2 && (ntb == 1 || ntb == 2) && cb < 3));
+}
+inline float pdsch_tx_sm_scale(float scaling, uint32_t nl, uint32_t cb)
+{
+  return nl == 2 && cb != 0 ? scaling / 2.0f : (float)((double)scaling * 0.70710678118654752440);
+}
 hipError_t pdsch_tx_launch(const PdschTx* d_items, uint32_t nitems, uint32_t max_nre, hipStream_t stream);
 // CRS of ports 0..nports-1 (1, 2 or 4) into grids [nsf][nports][2 nsymb][12 nof_prb] (nsymb = 7 normal CP, 6
 // extended); d_sf_idx[sf] = tti % 10

@@ -1156,9 +1156,24 @@ __global__ __launch_bounds__(LLR_THREADS) void pdsch_tx_kernel(const PdschTx* __
     return;
   }
   float2 a[TX_SPT], b[TX_SPT];
-  tx_symbols(t.e[0], t.seed[0], t.mod[0], k0, t.nre, a);
-  if (t.scheme == 3) {
-    tx_symbols(t.e[1], t.seed[1], t.mod[1], k0, t.nre, b);
+  if (t.scheme == 2 && t.nl == 2 && t.ncw == 1) {
+    // one codeword on two layers (srsran_layermap_multiplex -> srsran_layermap_diversity, layermap.c:38-61):
+    // symbols 2i / 2i + 1 of its 2 nre go to layers 0 / 1
+    float2 c[TX_SPT], d[TX_SPT];
+    tx_symbols(t.e[0], t.seed[0], t.mod[0], 2 * k0, 2 * t.nre, c);
+    tx_symbols(t.e[0], t.seed[0], t.mod[0], 2 * k0 + TX_SPT, 2 * t.nre, d);
+#pragma unroll
+    for (int s = 0; s < TX_SPT / 2; s++) {
+      a[s]              = c[2 * s];
+      b[s]              = c[2 * s + 1];
+      a[s + TX_SPT / 2] = d[2 * s];
+      b[s + TX_SPT / 2] = d[2 * s + 1];
+    }
+  } else {
+    tx_symbols(t.e[0], t.seed[0], t.mod[0], k0, t.nre, a);
+    if (t.scheme == 3 || (t.scheme == 2 && t.nl == 2)) {
+      tx_symbols(t.e[1], t.seed[1], t.mod[1], k0, t.nre, b);
+    }
   }
   const float sc = t.scaling;
 #pragma unroll
@@ -1177,6 +1192,23 @@ __global__ __launch_bounds__(LLR_THREADS) void pdsch_tx_kernel(const PdschTx* __
                                  : make_float2((a[s].x - b[s].x) * nm, (a[s].y - b[s].y) * nm);
       t.grid[0][g] = y0;
       t.grid[1][g] = y1;
+    } else if (t.scheme == 2) {  // srsran_precoding_multiplex, 2 ports (precoding.c:2087-2211)
+      const float  h = t.div_scale;
+      const float2 x0 = a[s];
+      if (t.nl == 1) {  // y0 = x h; y1 = {+1, -1, +j, -j} x h
+        t.grid[0][g] = make_float2(x0.x * h, x0.y * h);
+        t.grid[1][g] = t.cb == 0   ? make_float2(x0.x * h, x0.y * h)
+                       : t.cb == 1 ? make_float2(-(x0.x * h), -(x0.y * h))
+                       : t.cb == 2 ? make_float2(-(x0.y * h), x0.x * h)
+                                   : make_float2(x0.y * h, -(x0.x * h));
+      } else if (t.cb == 0) {
+        t.grid[0][g] = make_float2(x0.x * h, x0.y * h);
+        t.grid[1][g] = make_float2(b[s].x * h, b[s].y * h);
+      } else {  // (x0 + x1) h; (x0 - x1) h, times j for codebook 2
+        const float2 d = make_float2(x0.x - b[s].x, x0.y - b[s].y);
+        t.grid[0][g]   = make_float2((x0.x + b[s].x) * h, (x0.y + b[s].y) * h);
+        t.grid[1][g]   = t.cb == 1 ? make_float2(d.x * h, d.y * h) : make_float2(-d.y * h, d.x * h);
+      }
     } else if (t.scheme == 4) {  // transmit diversity, 4 ports (layermap.c:38-47 + precoding.c:1961-1988):
                                  // groups (4i .. 4i+3) of the codeword, SFBC on ports (0, 2) then (1, 3)
       const float  h  = t.div_scale;

@@ -869,6 +869,9 @@ int srsran_pdsch_encode(srsran_pdsch_t*     q,
     scheme = 4;
   } else if (gr.tx_scheme == SRSRAN_TXSCHEME_CDD && P == 2 && gr.nof_tb == 2 && gr.nof_layers == 2) {
     scheme = 3;
+  } else if (gr.tx_scheme == SRSRAN_TXSCHEME_SPATIALMUX &&
+             pdsch_tx_sm_ok(P, gr.nof_layers, gr.nof_tb, gr.nof_tb == 1 ? gr.pmi : gr.pmi + 1)) {
+    scheme = 2;
   } else {
     fprintf(stderr, "[srsran_pdsch] encode: scheme %d with %u ports / %u TBs is not provided\n", (int)gr.tx_scheme, P,
             gr.nof_tb);
@@ -895,7 +898,14 @@ int srsran_pdsch_encode(srsran_pdsch_t*     q,
   it.scheme    = scheme;
   it.scaling   = scaling;
   it.div_scale = scheme == 4 ? (float)(scaling / 1.41421356237309504880) : (float)((double)scaling * 0.70710678118654752440);
-  size_t   off = align256((size_t)P * nsf_re * sizeof(float2));
+  if (scheme == 2) {
+    it.nl        = gr.nof_layers;
+    it.ncw       = gr.nof_tb;
+    it.cb        = gr.nof_tb == 1 ? gr.pmi : gr.pmi + 1;
+    it.div_scale = pdsch_tx_sm_scale(scaling, it.nl, it.cb);
+  }
+  const uint32_t lpc = scheme == 2 ? gr.nof_layers / gr.nof_tb : 1;  // SM: layers of nre symbols a codeword
+  size_t   off =align256((size_t)P * nsf_re * sizeof(float2));
   size_t   o_idx = off;
   off += align256((size_t)nre * sizeof(uint32_t));
   size_t   o_item = off;
@@ -908,7 +918,7 @@ int srsran_pdsch_encode(srsran_pdsch_t*     q,
       continue;
     }
     const uint32_t Qm = srsran_mod_bits_x_symbol(tb.mod), Nl = gr.nof_layers != gr.nof_tb ? 2 : 1;
-    if (!data[t] || Qm == 0 || tb.tbs <= 0 || tb.nof_bits != nre * Qm || cw >= 2) {
+    if (!data[t] || Qm == 0 || tb.tbs <= 0 || tb.nof_bits != nre * Qm * lpc || cw >= 2) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
     o_data.push_back(off);
@@ -920,7 +930,7 @@ int srsran_pdsch_encode(srsran_pdsch_t*     q,
     it.mod[cw]  = (int)tb.mod;
     cw++;
   }
-  if ((scheme == 3) != (cw == 2) || !grow_dev((void**)&g->d_work, &g->work_cap, off) ||
+  if (cw != (scheme == 3 ? 2u : scheme == 2 ? gr.nof_tb : 1u) || !grow_dev((void**)&g->d_work, &g->work_cap, off) ||
       srsran_amd::handoff(g->ho, g->stream) != hipSuccess) {  // d_work: after the batches queued elsewhere
     return SRSRAN_ERROR;
   }

@@ -45,6 +45,15 @@ int chest_dl_gpu_estimate_batch_inline(srsran_chest_dl_t*           q,
 // the estimator options the batch estimator takes (the same check it makes, without launching anything; prints
 // the reason when it returns false)
 bool chest_batch_cfg_supported(const srsran_chest_dl_t* q, const srsran_chest_dl_cfg_t* cfg, int full_grid);
+// the device estimate the last host-synchronous srsran_chest_dl_estimate(_cfg) left (complete when it returned):
+// rows [port][rx] of 2 nsymb x 12 nof_prb, whatever the estimator algorithm (chest_api.cpp)
+const float2* chest_dl_gpu_last_ce(const srsran_chest_dl_t* q);
+
+// ---- channel-state feedback (csi_api.cpp) ----
+// one subframe's record from device rows h[port][rx] (row 2 port + rx at d_ce + that * row_stride; index j reads
+// row[j % row_len]) and a host noise estimate: kernel on the null stream, 64-byte readback, host-synchronous
+int csi_from_device(const float2* d_ce, size_t row_stride, uint32_t row_len, uint32_t nof_symbols, float noise,
+                    srsran_csi_gpu_t* out);
 
 }  // namespace srsran_amd
 #endif

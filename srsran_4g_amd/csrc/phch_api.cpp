@@ -92,6 +92,11 @@ bool pred_setup(PredArgs& a, int nrx, int nports, int nlayers, int codebook, int
       a.norm   = 2.0f / scaling;  // precoding.c:1052
       return true;
     case SRSRAN_TXSCHEME_SPATIALMUX:
+      if (nports == 2 && nrx == 2 && nlayers == 1 && codebook >= 0 && codebook <= 3) {
+        a.scheme = 5;  // one layer: srsran_predecoding_multiplex_2x1_mrc_csi over both rx antennas
+        a.norm   = (float)1.41421356237309504880 / scaling;  // precoding.c:1735
+        return true;
+      }
       if (nports != 2 || nrx != 2 || nlayers != 2 || codebook < 0 || codebook > 2) {
         return false;
       }

@@ -19,6 +19,7 @@
 
 #include "../../include/srsran_pdcch.h"
 #include "chest_kernel.h"
+#include "csi_kernel.h"
 #include "pdsch_internal.h"
 #include "stage_copy.h"
 #include "stage_timing.h"
@@ -42,6 +43,11 @@ struct UeDlGpu {
   float*     d_res  = nullptr;
   uint32_t   cap    = 0;  // subframes
   bool       cap_full = false;  // d_ce sized for full-grid (INTERPOLATE) estimates
+  // what the channel-state feedback reads: the last batch's subframes in d_ce / d_res and their estimate form
+  // (srsran_ue_dl_gpu_csi_batch), and whether a host-synchronous estimate was made (srsran_ue_dl_select_ri)
+  uint32_t   last_nsf  = 0;
+  bool       last_full = false;
+  bool       have_est  = false;
   // control channels (srsran_ue_dl_t::regs / pcfich / pdcch of the reference)
   srsran_regs_t         regs{};
   srsran_pcfich_t       pcfich{};
@@ -255,6 +261,8 @@ int srsran_ue_dl_set_cell(srsran_ue_dl_t* q, srsran_cell_t cell)
   UeDlGpu* g = (UeDlGpu*)q->gpu;
   q->cell    = cell;
   g->cap     = 0;  // buffer shapes depend on the cell
+  g->last_nsf = 0;
+  g->have_est = false;
   // control channels: 1, 2 or 4 ports, normal or extended PHICH duration (others: PDSCH only, CFI from the caller);
   // the REG tables of ue_dl.c:190-203 (SRSRAN_MI_NOF_REGS: 1 FDD, 6 TDD -- the m_i = 0 / 2 ones kept for FDD too,
   // srsran_ue_dl_set_mi_manual; the two-symbol PHICH ones only where MI_IDX can select them)
@@ -314,7 +322,8 @@ static int fft_estimate(srsran_ue_dl_t* q, srsran_dl_sf_cfg_t* sf, srsran_ue_dl_
     return SRSRAN_ERROR;
   }
   // estimate_pdcch_pcfich (ue_dl.c:315-347): PCFICH -> sf->cfi, then the PDCCH LLRs
-  UeDlGpu* g = (UeDlGpu*)q->gpu;
+  UeDlGpu* g  = (UeDlGpu*)q->gpu;
+  g->have_est = true;
   if (!g->ctrl_cell) {
     return sf->cfi >= 1 && sf->cfi <= 3 ? SRSRAN_SUCCESS : SRSRAN_ERROR;  // CFI from the caller
   }
@@ -401,6 +410,8 @@ static int decode_batch(srsran_ue_dl_t*              q,
   if (!grow(q, g, nof_sf, full)) {
     return SRSRAN_ERROR;
   }
+  g->last_nsf  = nof_sf;
+  g->last_full = full;
   const size_t nre = 12 * (size_t)q->cell.nof_prb, nrx = q->nof_rx_antennas, np = q->cell.nof_ports;
   const size_t rows = 2 * SRSRAN_CP_NSYMB(q->cell.cp);  // grid symbols per subframe
   std::vector<srsran_pdsch_gpu_sf_t> ps(nof_sf);
@@ -536,6 +547,124 @@ int srsran_ue_dl_gpu_decode_batch(srsran_ue_dl_t*              q,
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   return decode_batch(q, cfg, nof_sf, sfs, d_samples, nullptr, 1.0f, cfo, d_result, d_avg_noi, stream);
+}
+
+// ---------------- channel-state feedback (ue_dl.c:750-843) ----------------
+// 0: nothing to do (fewer than 2 ports, SRSRAN_SUCCESS as the reference); 1: 2 ports x 2 rx; < 0: refused
+static int csi_shape(const srsran_ue_dl_t* q)
+{
+  if (!q || !q->gpu) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (q->cell.nof_ports < 2) {
+    return 0;
+  }
+  if (q->cell.nof_ports != 2 || q->nof_rx_antennas != 2) {
+    fprintf(stderr, "[srsran_ue_dl] RI / PMI selection: 2 ports x 2 rx antennas only (%u x %u)\n", q->cell.nof_ports,
+            q->nof_rx_antennas);
+    return SRSRAN_ERROR;
+  }
+  return 1;
+}
+
+// the record of the device estimate the last srsran_ue_dl_decode_fft_estimate left
+static int csi_last_estimate(srsran_ue_dl_t* q, srsran_csi_gpu_t* o)
+{
+  const UeDlGpu* g    = (const UeDlGpu*)q->gpu;
+  const float2*  d_ce = srsran_amd::chest_dl_gpu_last_ce(&q->chest);
+  if (!g->have_est || !d_ce) {
+    fprintf(stderr, "[srsran_ue_dl] RI / PMI selection before srsran_ue_dl_decode_fft_estimate\n");
+    return SRSRAN_ERROR;
+  }
+  const uint32_t n = SRSRAN_NOF_RE(q->cell);
+  return srsran_amd::csi_from_device(d_ce, n, n, n, q->chest_res.noise_estimate, o);
+}
+
+int srsran_ue_dl_select_ri(srsran_ue_dl_t* q, uint32_t* ri, float* cn)
+{
+  const int shape = csi_shape(q);
+  if (shape <= 0) {
+    return shape;
+  }
+  srsran_csi_gpu_t o;
+  const int        ret = csi_last_estimate(q, &o);
+  if (ret == SRSRAN_SUCCESS) {
+    if (cn) {
+      *cn = o.cn;
+    }
+    if (ri) {
+      *ri = o.ri_cn;
+    }
+  }
+  return ret;
+}
+
+int srsran_ue_dl_select_ri_pmi(srsran_ue_dl_t* q, uint32_t* ri, uint32_t* pmi, float* sinr_db)
+{
+  const int shape = csi_shape(q);
+  if (shape <= 0) {
+    return shape;
+  }
+  srsran_csi_gpu_t o;
+  const int        ret = csi_last_estimate(q, &o);
+  if (ret == SRSRAN_SUCCESS) {
+    if (ri) {
+      *ri = o.ri;
+    }
+    if (pmi) {
+      *pmi = o.pmi;
+    }
+    if (sinr_db) {
+      *sinr_db = o.sinr_db;
+    }
+  }
+  return ret;
+}
+
+int srsran_ue_dl_gpu_csi_batch(srsran_ue_dl_t* q, uint32_t nof_sf, srsran_csi_gpu_t* d_csi, void* stream)
+{
+  const int shape = csi_shape(q);
+  if (shape <= 0) {
+    return shape;
+  }
+  UeDlGpu* g = (UeDlGpu*)q->gpu;
+  if (nof_sf == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!d_csi || nof_sf > g->last_nsf || !g->d_ce || !g->d_res) {
+    fprintf(stderr, "[srsran_ue_dl] csi_batch: %u subframes, the last batch left %u\n", nof_sf, g->last_nsf);
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  const uint32_t nre = 12 * q->cell.nof_prb, n = SRSRAN_NOF_RE(q->cell);
+  srsran_amd::CsiArgs a{};
+  a.ce           = g->d_ce;
+  a.row_stride   = g->last_full ? n : nre;
+  a.sf_stride    = 4 * a.row_stride;  // [port][rx] rows of a 2 x 2 cell
+  a.row_len      = g->last_full ? n : nre;
+  a.nof_symbols  = n;
+  a.noise        = g->d_res;  // [sf][noise_estimate, rsrp, rssi, cfo]
+  a.noise_stride = 4;
+  a.out          = d_csi;
+  if (srsran_amd::handoff(g->ho, (hipStream_t)stream) != hipSuccess ||
+      srsran_amd::csi_launch(a, nof_sf, (hipStream_t)stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_ue_dl_gpu_last_ce(srsran_ue_dl_t* q, uint32_t sf, const cf_t** d_ce, uint32_t* row_len, const float** d_noise)
+{
+  if (!q || !q->gpu || !d_ce || !row_len || !d_noise) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  const UeDlGpu* g = (const UeDlGpu*)q->gpu;
+  if (sf >= g->last_nsf || !g->d_ce || !g->d_res) {
+    return SRSRAN_ERROR;
+  }
+  *row_len = g->last_full ? SRSRAN_NOF_RE(q->cell) : 12 * q->cell.nof_prb;
+  *d_ce    = (const cf_t*)(g->d_ce + (size_t)sf * q->cell.nof_ports * q->nof_rx_antennas * *row_len);
+  *d_noise = g->d_res + 4 * (size_t)sf;
+  return SRSRAN_SUCCESS;
 }
 
 int srsran_gpu_worker_stream_create(void** stream)

@@ -72,7 +72,9 @@ class EnbDl:
 
     def tx_batch(self, sfs, d_samples, scale=0.0, stream=None, pdsch_scaling=0.0):
         """sfs: list of (tti, cfi, srsran_pdsch_cfg_t or None, [device payload pointers][, ctrl]) with ctrl =
-        (put_base, [srsran_dci_msg_t, ...]) or None; pdsch_scaling: every subframe's precoder scaling (<= 0: 1)"""
+        (put_base, [srsran_dci_msg_t, ...]) or None; pdsch_scaling: every subframe's precoder scaling (<= 0: 1).
+        The transmission scheme is the grant's: cfg.grant.tx_scheme with nof_layers, nof_tb and pmi (ue_dl.pdsch_cfg
+        scheme="port0" / "diversity" / "cdd" / "sm", pmi=, layers= for one codeword on two layers)"""
         arr = (srsran_enb_dl_gpu_sf_t * len(sfs))()
         self._keep = []
         for i, sf in enumerate(sfs):

@@ -110,6 +110,58 @@ class srsran_ue_dl_gpu_sf_t(ctypes.Structure):
                 ("d_payload", ctypes.c_void_p * 2), ("new_data", u32 * 2), ("tdd_config", srsran_tdd_config_t)]
 
 
+class srsran_csi_gpu_t(ctypes.Structure):  # one subframe's RI / PMI / SINR record (64 bytes)
+    _fields_ = [("sinr_1l", ctypes.c_float * 4), ("sinr_2l", ctypes.c_float * 2), ("cn", ctypes.c_float),
+                ("sinr_db", ctypes.c_float), ("pmi_1l", u32), ("pmi_2l", u32), ("ri_cn", u32), ("ri", u32),
+                ("pmi", u32), ("cn_count", u32), ("reserved", u32 * 2)]
+
+
+CSI_DTYPE = np.dtype([("sinr_1l", np.float32, 4), ("sinr_2l", np.float32, 2), ("cn", np.float32),
+                      ("sinr_db", np.float32), ("pmi_1l", np.uint32), ("pmi_2l", np.uint32), ("ri_cn", np.uint32),
+                      ("ri", np.uint32), ("pmi", np.uint32), ("cn_count", np.uint32), ("reserved", np.uint32, 2)])
+
+
+def _h_rows(h):
+    """h[port][rx] -> (the cf_t* [4][4] argument, the arrays it points into)"""
+    rows = [[np.ascontiguousarray(h[p][r], np.complex64) for r in range(2)] for p in range(2)]
+    ptrs = ((ctypes.c_void_p * MAX_PORTS) * MAX_PORTS)()
+    for p in range(2):
+        for r in range(2):
+            ptrs[p][r] = rows[p][r].ctypes.data
+    return ptrs, rows
+
+
+def precoding_pmi_select(h, noise, nof_layers, nof_symbols=None):
+    """srsran_precoding_pmi_select on host estimates h[port][rx] -> (ret, pmi, sinr list)"""
+    ptrs, rows = _h_rows(h)
+    n = len(rows[0][0]) if nof_symbols is None else nof_symbols
+    pmi, sinr = u32(0), (ctypes.c_float * 4)()
+    ret = lib().srsran_precoding_pmi_select(ctypes.addressof(ptrs), n, noise, nof_layers, ctypes.byref(pmi), sinr)
+    return ret, pmi.value, [np.float32(sinr[i]) for i in range(max(ret, 0))]
+
+
+def precoding_cn(h, ntx=2, nrx=2, nof_symbols=None):
+    """srsran_precoding_cn on host estimates h[port][rx] -> (ret, condition number in dB)"""
+    ptrs, rows = _h_rows(h)
+    n = len(rows[0][0]) if nof_symbols is None else nof_symbols
+    cn = ctypes.c_float(0)
+    ret = lib().srsran_precoding_cn(ctypes.addressof(ptrs), ntx, nrx, n, ctypes.byref(cn))
+    return ret, np.float32(cn.value)
+
+
+def precoding_csi_2x2(h, noise, nof_symbols=None):
+    """srsran_precoding_csi_2x2 on host estimates h[port][rx] -> (ret, the record as a CSI_DTYPE scalar)"""
+    ptrs, rows = _h_rows(h)
+    n = len(rows[0][0]) if nof_symbols is None else nof_symbols
+    rec = np.zeros(1, CSI_DTYPE)
+    ret = lib().srsran_precoding_csi_2x2(ctypes.addressof(ptrs), n, noise, rec.ctypes.data)
+    return ret, rec[0]
+
+
+def cqi_from_snr(snr):
+    return int(lib().srsran_cqi_from_snr(snr))
+
+
 _bound = False
 
 
@@ -213,6 +265,20 @@ def lib():
             "srsran_ue_dl_gpu_decode_batch": ([UE, ctypes.POINTER(srsran_ue_dl_cfg_t), u32,
                                                ctypes.POINTER(srsran_ue_dl_gpu_sf_t), P, ctypes.c_float, P, P, P],
                                               ctypes.c_int),
+            "srsran_precoding_pmi_select": ([P, u32, ctypes.c_float, ctypes.c_int, ctypes.POINTER(u32),
+                                             ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "srsran_precoding_cn": ([P, u32, u32, u32, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "srsran_precoding_csi_2x2": ([P, u32, ctypes.c_float, P], ctypes.c_int),
+            "srsran_pdsch_select_pmi": ([PD, RES, u32, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_float)],
+                                        ctypes.c_int),
+            "srsran_pdsch_compute_cn": ([PD, RES, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "srsran_ue_dl_select_ri": ([UE, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "srsran_ue_dl_select_ri_pmi": ([UE, ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                            ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+            "srsran_ue_dl_gpu_csi_batch": ([UE, u32, P, P], ctypes.c_int),
+            "srsran_ue_dl_gpu_last_ce": ([UE, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32),
+                                          ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+            "srsran_cqi_from_snr": ([ctypes.c_float], ctypes.c_uint8),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -431,11 +497,12 @@ MOD_FROM_QM = {1: 0, 2: 1, 4: 2, 6: 3, 8: 4}
 
 def pdsch_cfg(nof_prb, nof_re, tbs, Qm, rv=(0, 0), scheme="cdd", pmi=0, rnti=0x1234, max_iterations=8,
               csi_enable=True, power_scale=False, p_a=0.0, p_b=0, softbuffers=(), zf=False, cp=0, nof_ports=2,
-              meas_evm=False, nsl=None):
+              meas_evm=False, nsl=None, layers=None):
     """srsran_pdsch_cfg_t for a full-bandwidth grant of len(tbs) codewords on as many layers
     (srsUE defaults: csi_enable, 8 half-iterations, MMSE, no power scaling); cp=1: extended CP;
     transmit diversity runs on nof_ports layers (2 or 4); nsl: the grant's symbols per slot (a TDD special
-    subframe's DwPTS, srsran_ra_dl_compute_nof_re)."""
+    subframe's DwPTS, srsran_ra_dl_compute_nof_re); layers: the transmitter's form of fewer codewords than layers
+    (spatial multiplexing: nof_layers = layers, every codeword nof_re x Qm x layers / len(tbs) bits)."""
     c = srsran_pdsch_cfg_t()
     g = c.grant
     g.tx_scheme = SCHEME[scheme]
@@ -458,6 +525,10 @@ def pdsch_cfg(nof_prb, nof_re, tbs, Qm, rv=(0, 0), scheme="cdd", pmi=0, rnti=0x1
         tb.nof_bits = nof_re * Qm[i]
         tb.cw_idx = i
         tb.enabled = True
+    if layers is not None:
+        g.nof_layers = layers
+        for i in range(len(tbs)):
+            g.tb[i].nof_bits = nof_re * Qm[i] * layers // len(tbs)
     c.rnti = rnti
     c.max_nof_iterations = max_iterations
     c.decoder_type = 0 if zf else 1
@@ -683,6 +754,46 @@ class UeDl:
         arr = sfs if isinstance(sfs, ctypes.Array) else self.batch_entries(sfs, self.tdd)
         return lib().srsran_ue_dl_gpu_decode_batch_sc16(ctypes.byref(self.q), ctypes.byref(self.cfg), len(arr), arr,
                                                         d_samples, scale, cfo, d_result, d_avg, stream)
+
+    def select_ri(self):
+        """srsran_ue_dl_select_ri on the last fft_estimate's device estimate -> (ret, ri, cn in dB)"""
+        ri, cn = u32(0), ctypes.c_float(0)
+        ret = lib().srsran_ue_dl_select_ri(ctypes.byref(self.q), ctypes.byref(ri), ctypes.byref(cn))
+        return ret, ri.value, cn.value
+
+    def select_ri_pmi(self):
+        """srsran_ue_dl_select_ri_pmi on the last fft_estimate's device estimate -> (ret, ri, pmi, sinr in dB)"""
+        ri, pmi, db = u32(0), u32(0), ctypes.c_float(0)
+        ret = lib().srsran_ue_dl_select_ri_pmi(ctypes.byref(self.q), ctypes.byref(ri), ctypes.byref(pmi),
+                                               ctypes.byref(db))
+        return ret, ri.value, pmi.value, db.value
+
+    def csi_batch(self, nof_sf, d_csi, stream=None):
+        """srsran_ue_dl_gpu_csi_batch: nof_sf srsran_csi_gpu_t records (CSI_DTYPE) of the last gpu_decode_batch into
+        the device buffer d_csi (64 bytes a subframe); asynchronous on stream"""
+        return lib().srsran_ue_dl_gpu_csi_batch(ctypes.byref(self.q), nof_sf, d_csi, stream)
+
+    def last_ce(self, sf):
+        """srsran_ue_dl_gpu_last_ce: (device pointer of subframe sf's [port][rx] estimate rows, row length, device
+        pointer of its noise estimate) of the last gpu_decode_batch"""
+        d_ce, n, d_noise = ctypes.c_void_p(), u32(0), ctypes.c_void_p()
+        if lib().srsran_ue_dl_gpu_last_ce(ctypes.byref(self.q), sf, ctypes.byref(d_ce), ctypes.byref(n),
+                                          ctypes.byref(d_noise)):
+            raise RuntimeError(f"no estimate for subframe {sf} in the last batch")
+        return d_ce.value, n.value, d_noise.value
+
+    def pdsch_select_pmi(self, nof_layers):
+        """srsran_pdsch_select_pmi on the host estimate (chest_res) -> (ret, pmi, sinr list)"""
+        pmi, sinr = u32(0), (ctypes.c_float * 4)()
+        ret = lib().srsran_pdsch_select_pmi(ctypes.byref(self.q.pdsch), ctypes.byref(self.q.chest_res), nof_layers,
+                                            ctypes.byref(pmi), sinr)
+        return ret, pmi.value, [np.float32(sinr[i]) for i in range(4 if nof_layers == 1 else 2)]
+
+    def pdsch_compute_cn(self):
+        """srsran_pdsch_compute_cn on the host estimate (chest_res) -> (ret, cn in dB)"""
+        cn = ctypes.c_float(0)
+        ret = lib().srsran_pdsch_compute_cn(ctypes.byref(self.q.pdsch), ctypes.byref(self.q.chest_res), ctypes.byref(cn))
+        return ret, np.float32(cn.value)
 
     def last_llr(self, sf, tb):
         """srsran_pdsch_gpu_last_llr of the UE's PDSCH object after a batch: (device pointer, count)"""

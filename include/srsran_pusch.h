@@ -100,7 +100,8 @@ int  srsran_chest_ul_res_init(srsran_chest_ul_res_t* q, uint32_t max_prb);
 void srsran_chest_ul_res_set_identity(srsran_chest_ul_res_t* q);
 void srsran_chest_ul_res_free(srsran_chest_ul_res_t* q);
 int  srsran_chest_ul_set_cell(srsran_chest_ul_t* q, srsran_cell_t cell);
-/* srs_cfg: SRS is not provided; pass NULL (a non-NULL srs_cfg is ignored) */
+/* srs_cfg: SRS is not provided; pass NULL (a non-NULL srs_cfg is ignored).  PUCCH estimation on the same objects:
+ * srsran_chest_ul_estimate_pucch in srsran_pucch.h */
 void srsran_chest_ul_pregen(srsran_chest_ul_t* q, srsran_refsignal_dmrs_pusch_cfg_t* cfg, void* srs_cfg);
 /* chest_ul.c:398-433.  cfg->use_cedron_alg with cfg->meas_ta_en is not provided (FFTW-based in the
  * reference): SRSRAN_ERROR. */

@@ -319,6 +319,23 @@ bool any_uci(const srsran_pusch_cfg_t* cfg)
 
 }  // namespace
 
+// what the PUCCH estimator (pucch_api.cpp) needs of the chest objects: the stream, a device
+// scratch of `bytes` (the grid buffer, grown), and a note that res->ce was rewritten on the host
+namespace srsran_amd {
+hipStream_t chest_ul_stream(srsran_chest_ul_t* q) { return q && q->gpu ? ((ChestUlGpu*)q->gpu)->stream : nullptr; }
+void*       chest_ul_scratch(srsran_chest_ul_t* q, size_t bytes)
+{
+  ChestUlGpu* g = (ChestUlGpu*)q->gpu;
+  return grow((void**)&g->d_grid, &g->grid_cap, bytes) ? (void*)g->d_grid : nullptr;
+}
+void chest_ul_res_host_changed(srsran_chest_ul_res_t* res)
+{
+  if (res && res->gpu) {
+    ((ChestUlResGpu*)res->gpu)->valid = false;
+  }
+}
+}  // namespace srsran_amd
+
 extern "C" {
 
 bool srsran_dft_precoding_valid_prb(uint32_t nof_prb)

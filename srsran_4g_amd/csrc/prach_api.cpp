@@ -1,0 +1,662 @@
+// srsran_4g_amd/csrc/prach_api.cpp -- C-ABI host side of PRACH (include/srsran_prach.h).
+//
+// prach.c:108-186, 293 (FDD occasion helpers), 450-747 (sequences, set_cfg), 749-793 (gen), 800-1012 (detect).
+// The transforms run in prach_kernel.hip; the threshold compare, the (root, window) ordering and the offset
+// arithmetic of srsran_prach_process (prach.c:928-957) run here over the kernels' per-window records.
+// No FFTW, no CPU fallback.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/srsran_prach.h"
+#include "prach_kernel.h"
+
+using namespace srsran_amd;
+
+#include "prach_tables.inc"
+
+namespace {
+
+constexpr uint32_t N_SEQS     = 64;
+constexpr uint32_t DELTA_F    = 15000;
+constexpr uint32_t DELTA_F_RA = 1250;
+constexpr uint32_t PHI        = 7;
+constexpr uint32_t MAX_ROOTS  = 838;
+constexpr float    LTE_TS     = 1.0f / (15000.0f * 2048.0f);  // phy_common.h:146
+constexpr float    DETECT_FACTOR = 18;                        // prach.c:35
+
+struct Metrics {
+  bool     valid = false;
+  uint32_t nof_roots = 0, nof_wins = 0;
+  float    ratio[PRACH_MAX_WIN];
+  uint32_t offset[PRACH_MAX_WIN];
+};
+
+struct PrachGpu {
+  hipStream_t stream = nullptr;
+  // per configuration
+  float2*  d_tw_n   = nullptr;  // N
+  float2*  d_tw_m   = nullptr;  // 12 N
+  float2*  d_tw839  = nullptr;  // exp(+2 pi i m / 839)
+  float2*  d_seqs   = nullptr;  // [64][839]
+  float2*  d_spec   = nullptr;  // [64][839]
+  uint32_t tw_N     = 0;        // the size d_tw_n / d_tw_m were built for
+  OfdmArgs fft      = {};  // only the plan is set (prach_kernel.h)
+  // host-synchronous calls
+  float2* d_sig = nullptr;  // 12 max_N (detect input)
+  float2* d_gen = nullptr;  // SRSRAN_PRACH_MAX_LEN scaled to max_N (gen output)
+  // batch workspace (of the batch's first object)
+  uint32_t     cap    = 0;
+  PrachOcc*    h_occ  = nullptr;  // pinned
+  PrachOcc*    d_occ  = nullptr;
+  PrachOccOut* h_out  = nullptr;  // pinned
+  PrachOccOut* d_out  = nullptr;
+  float2*      d_part = nullptr;  // [cap][12][839]
+  Metrics      metrics;
+  // srsran_prach_gpu_detect_time: events around the two kernels of a detect run on this object's stream
+  bool       timing = false;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  float      last_us = -1.f;
+};
+
+void release_batch(PrachGpu* g)
+{
+  hipHostFree(g->h_occ);
+  hipHostFree(g->h_out);
+  hipFree(g->d_occ);
+  hipFree(g->d_out);
+  hipFree(g->d_part);
+  g->h_occ = g->d_occ = nullptr;
+  g->h_out = g->d_out = nullptr;
+  g->d_part           = nullptr;
+  g->cap              = 0;
+}
+
+bool reserve(PrachGpu* g, uint32_t n)
+{
+  if (n <= g->cap) {
+    return true;
+  }
+  hipStreamSynchronize(g->stream);
+  release_batch(g);
+  uint32_t m = 16;
+  while (m < n) {
+    m *= 2;
+  }
+  if (hipHostMalloc((void**)&g->h_occ, m * sizeof(PrachOcc)) != hipSuccess ||
+      hipHostMalloc((void**)&g->h_out, m * sizeof(PrachOccOut)) != hipSuccess ||
+      hipMalloc((void**)&g->d_occ, m * sizeof(PrachOcc)) != hipSuccess ||
+      hipMalloc((void**)&g->d_out, m * sizeof(PrachOccOut)) != hipSuccess ||
+      hipMalloc((void**)&g->d_part, (size_t)m * PRACH_K * PRACH_NZC * sizeof(float2)) != hipSuccess) {
+    release_batch(g);
+    return false;
+  }
+  g->cap = m;
+  return true;
+}
+
+std::vector<float2> cexp_table(uint32_t n, double sign)
+{
+  std::vector<float2> h(n);
+  for (uint32_t m = 0; m < n; m++) {
+    const double ang = sign * 2.0 * M_PI * (double)m / (double)n;
+    h[m]             = make_float2((float)cos(ang), (float)sin(ang));
+  }
+  return h;
+}
+
+// The 64 preambles of a normal (unrestricted) cell, 36.211 5.7.2: each root yields floor(839 / N_cs) cyclic shifts
+// (one when N_cs = 0), roots taken in logical order from rsi on.  x_u(j) = exp(-i pi u j (j+1) / 839) comes from an
+// exact 1678-entry table indexed by u j (j+1) mod 1678, as prach.c:74-84 does it.
+void gen_seqs(srsran_prach_t* p)
+{
+  static const std::vector<float2> lut = cexp_table(2 * PRACH_NZC, -1.0);  // built once (thread-safe)
+  const uint32_t shifts = p->N_cs ? PRACH_NZC / p->N_cs : 1;
+  float2         root[PRACH_NZC];
+  float2*        seqs = (float2*)p->seqs;
+  p->N_roots          = 0;
+  for (uint32_t i = 0; i < N_SEQS; i++) {
+    if (i % shifts == 0) {
+      const uint32_t u = kPrachRoots[(p->rsi + i / shifts) % MAX_ROOTS];
+      for (uint32_t j = 0; j < PRACH_NZC; j++) {
+        root[j] = lut[(u * j * (j + 1)) % (2 * PRACH_NZC)];  // below 2^32 for u, j < 839
+      }
+      p->root_seqs_idx[p->N_roots++] = i;
+    }
+    const uint32_t shift = (i % shifts) * p->N_cs;
+    for (uint32_t j = 0; j < PRACH_NZC; j++) {
+      seqs[i * PRACH_NZC + j] = root[(j + shift) % PRACH_NZC];
+    }
+  }
+}
+
+// The first PRACH bin of the 12 N-point transform in natural order (36.211 5.7.3: bin phi + K (k_0 + 1/2), K = 12,
+// phi = 7, k_0 the first subcarrier of PRB freq_offset counted from the lower band edge; NR drops the half
+// subcarrier).  The reference indexes a DC-centred spectrum with it (prach.c:754-757, 993-996), whose index s holds
+// bin (s + 6 N) mod 12 N.  false: no room for 6 PRB at freq_offset.
+bool first_bin(const srsran_prach_t* p, uint32_t freq_offset, uint32_t* b0)
+{
+  const int      cell_prb = srsran_nof_prb(p->N_ifft_ul);  // the symbol-size convention may have changed since set_cfg
+  const uint32_t N = p->N_ifft_ul, M = p->N_ifft_prach;
+  if (cell_prb <= 0 || freq_offset + 6 > (uint32_t)cell_prb) {
+    return false;
+  }
+  const uint32_t first_sc = N / 2 + 12 * freq_offset - 6 * (uint32_t)cell_prb;  // of the N-point grid, DC at N / 2
+  const uint32_t centred  = PRACH_K * first_sc + PHI + (p->is_nr ? 0 : PRACH_K / 2);
+  *b0                     = (centred + M / 2) % M;
+  return true;
+}
+
+// The timing offset in seconds from the lag-1 sum of a root's product spectrum: its phase is 2 pi d / 839 for a
+// delay of d correlation samples.  The float / double operation order is that of prach.c:848-858 (the result is
+// compared bit for bit): three float products, a double division by 2 pi, roundf of the float, a float division.
+float freq_domain_offset_secs(const srsran_prach_t* p, float2 lag1)
+{
+  const float  srate_over_bw = (float)(p->N_ifft_ul * DELTA_F) / (float)(PRACH_NZC * DELTA_F_RA);
+  const double samples       = (srate_over_bw * atan2f(lag1.y, lag1.x) * p->N_zc) / (2 * M_PI);
+  return roundf((float)samples) / ((float)p->N_ifft_ul * DELTA_F);
+}
+
+// Table 5.7.1-2 by configuration mod 16: bit s set = subframe s carries an occasion (index 14's row is empty, as
+// the reference's; configuration 14 itself is handled by the caller), and the configurations of even frames only
+uint32_t occasion_mask(uint32_t config_idx)
+{
+  const int* row  = kPrachSf[config_idx % 16];
+  uint32_t   mask = 0;
+  for (int i = 0; i < row[0]; i++) {
+    mask |= 1u << row[1 + i];
+  }
+  return mask;
+}
+constexpr uint32_t EVEN_FRAMES_ONLY = (1u << 0) | (1u << 1) | (1u << 2) | (1u << 15);
+
+// subframes a preamble of this format spans: ceil((T_CP + T_SEQ) / 30720 T_s)
+uint32_t preamble_ttis(uint32_t format)
+{
+  return format < 4 ? (kPrachTcp[format] + kPrachTseq[format] + 30719) / 30720 : 0;
+}
+
+int check_occ(const srsran_prach_t* p, const void* signal, uint32_t sig_len, uint32_t freq_offset, uint32_t* b0)
+{
+  if (p == nullptr || p->gpu == nullptr || signal == nullptr || sig_len == 0) {
+    return SRSRAN_ERROR;
+  }
+  if (p->N_ifft_prach == 0) {
+    fprintf(stderr, "[srsran_prach] detect before srsran_prach_set_cfg\n");
+    return SRSRAN_ERROR;
+  }
+  if (sig_len < p->N_ifft_prach) {
+    fprintf(stderr, "[srsran_prach] srsran_prach_detect: Signal length is %u and should be %u\n", sig_len,
+            p->N_ifft_prach);
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (!first_bin(p, freq_offset, b0)) {
+    fprintf(stderr, "[srsran_prach] no space for PRACH: frequency offset=%u\n", freq_offset);
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// the batch on the first object's stream; every entry checked by the caller
+int detect_core(uint32_t nocc, const srsran_prach_gpu_occ_t* occ, const uint32_t* b0, srsran_prach_gpu_res_t* res)
+{
+  PrachGpu* g = (PrachGpu*)occ[0].prach->gpu;
+  if (!reserve(g, nocc)) {
+    return SRSRAN_ERROR;
+  }
+  uint32_t max_roots = 1;
+  for (uint32_t i = 0; i < nocc; i++) {
+    const srsran_prach_t* p  = occ[i].prach;
+    const PrachGpu*       gp = (const PrachGpu*)p->gpu;
+    PrachOcc&             d  = g->h_occ[i];
+    d.fft                    = gp->fft;
+    d.sig                    = (const float2*)occ[i].d_signal;
+    d.tw_m                   = gp->d_tw_m;
+    d.root_spec              = gp->d_spec;
+    memcpy(d.root_idx, p->root_seqs_idx, sizeof(d.root_idx));
+    d.b0      = b0[i];
+    d.n_roots = p->num_ra_preambles;
+    d.n_cs    = p->N_cs;
+    d.n_wins  = p->N_cs ? p->N_zc / p->N_cs : 1;
+    d.scale   = 1.0f / sqrtf((float)p->N_ifft_prach);
+    max_roots = d.n_roots > max_roots ? d.n_roots : max_roots;
+  }
+  const bool timed = g->timing && g->ev0 && g->ev1;
+  if (hipMemcpyAsync(g->d_occ, g->h_occ, nocc * sizeof(PrachOcc), hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+      (timed && hipEventRecord(g->ev0, g->stream) != hipSuccess) ||
+      prach_bins_launch(g->d_occ, g->d_part, nocc, g->stream) != hipSuccess ||
+      prach_search_launch(g->d_occ, g->d_part, g->d_tw839, g->d_out, nocc, max_roots, g->stream) != hipSuccess ||
+      (timed && hipEventRecord(g->ev1, g->stream) != hipSuccess) ||
+      hipMemcpyAsync(g->h_out, g->d_out, nocc * sizeof(PrachOccOut), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+      hipStreamSynchronize(g->stream) != hipSuccess) {
+    fprintf(stderr, "[srsran_prach] detect: %s\n", hipGetErrorString(hipGetLastError()));
+    return SRSRAN_ERROR;
+  }
+  if (timed) {
+    float ms   = 0.f;
+    g->last_us = hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess ? ms * 1e3f : -1.f;
+  }
+  for (uint32_t e = 0; e < nocc; e++) {
+    srsran_prach_t*    p      = occ[e].prach;
+    const PrachOccOut& o      = g->h_out[e];
+    const uint32_t     n_wins = g->h_occ[e].n_wins;
+    Metrics&           m      = ((PrachGpu*)p->gpu)->metrics;
+    srsran_prach_gpu_res_t& r = res[e];
+    r.nof_det   = 0;
+    m.nof_roots = p->num_ra_preambles;
+    m.nof_wins  = n_wins;
+    m.valid     = true;
+    for (uint32_t i = 0; i < p->num_ra_preambles; i++) {
+      const float corr_ave = o.avg[i];
+      for (uint32_t j = 0; j < n_wins && i * n_wins + j < PRACH_MAX_WIN; j++) {
+        const uint32_t w = i * n_wins + j;
+        m.ratio[w]       = o.peak[w] / corr_ave;
+        m.offset[w]      = o.off[w];
+        if (o.peak[w] > p->detect_factor * corr_ave && r.nof_det < SRSRAN_PRACH_GPU_MAX_DET) {
+          r.indices[r.nof_det]     = w;
+          r.peak_to_avg[r.nof_det] = o.peak[w] / corr_ave;
+          r.t_offsets[r.nof_det]   = p->freq_domain_offset_calc
+                                         ? freq_domain_offset_secs(p, o.cross[i])
+                                         : (float)o.off[w] / (float)(DELTA_F_RA * p->N_zc);  // prach.c:840-844
+          r.nof_det++;
+        }
+      }
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
+void fill_fft(PrachGpu* g, uint32_t N)
+{
+  g->fft.tw      = g->d_tw_n;
+  g->fft.N       = N;
+  g->fft.nstages = ofdm_plan(N, g->fft.radix, g->fft.ns_magic);
+}
+
+int gen_device(srsran_prach_t* p, uint32_t seq_index, uint32_t freq_offset, float2* d_out)
+{
+  PrachGpu* g = (PrachGpu*)p->gpu;
+  uint32_t  b0 = 0;
+  if (!first_bin(p, freq_offset, &b0)) {
+    fprintf(stderr, "[srsran_prach] Error no space for PRACH: frequency offset=%u, N_rb_ul=%d\n", freq_offset,
+            srsran_nof_prb(p->N_ifft_ul));
+    return SRSRAN_ERROR;
+  }
+  PrachGenArgs a;
+  a.fft   = g->fft;
+  a.tw_m  = g->d_tw_m;
+  a.spec  = g->d_spec + (size_t)seq_index * PRACH_NZC;
+  a.out   = d_out;
+  a.b0    = b0;
+  a.n_cp  = p->N_cp;
+  a.n_seq = p->N_seq;
+  a.scale = 1.0f / sqrtf((float)p->N_ifft_prach);
+  if (prach_gen_launch(a, g->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t srsran_prach_get_preamble_format(uint32_t config_idx)
+{
+  return config_idx / 16;
+}
+
+srsran_prach_sfn_t srsran_prach_get_sfn(uint32_t config_idx)
+{
+  return ((EVEN_FRAMES_ONLY >> (config_idx % 16)) & 1) ? SRSRAN_PRACH_SFN_EVEN : SRSRAN_PRACH_SFN_ANY;
+}
+
+bool srsran_prach_tti_opportunity(srsran_prach_t* p, uint32_t current_tti, int allowed_subframe)
+{
+  if (p == nullptr || p->tdd_config.configured || p->is_nr) {
+    return false;
+  }
+  return srsran_prach_tti_opportunity_config_fdd(p->config_idx, current_tti, allowed_subframe);
+}
+
+bool srsran_prach_tti_opportunity_config_fdd(uint32_t config_idx, uint32_t current_tti, int allowed_subframe)
+{
+  if (config_idx == 14) {  // every subframe, whatever allowed_subframe says (prach.c:154)
+    return true;
+  }
+  const uint32_t frame = current_tti / 10, sf = current_tti % 10;
+  if (allowed_subframe != -1 && (int)sf != allowed_subframe) {
+    return false;
+  }
+  if (srsran_prach_get_sfn(config_idx) == SRSRAN_PRACH_SFN_EVEN && (frame & 1)) {
+    return false;
+  }
+  return (occasion_mask(config_idx) >> sf) & 1;
+}
+
+bool srsran_prach_in_window_config_fdd(uint32_t config_idx, uint32_t current_tti, int allowed_subframe)
+{
+  // inside a preamble that began at most preamble_ttis - 1 subframes ago (the TTI wraps as the reference's does)
+  const uint32_t dur = preamble_ttis(srsran_prach_get_preamble_format(config_idx));
+  for (uint32_t age = 0; age < (dur ? dur : 1); age++) {
+    if (srsran_prach_tti_opportunity_config_fdd(config_idx, current_tti - age, allowed_subframe)) {
+      return true;
+    }
+  }
+  return false;
+}
+
+void srsran_prach_sf_config(uint32_t config_idx, srsran_prach_sf_config_t* sf_config)
+{
+  const int* row    = kPrachSf[config_idx % 16];
+  sf_config->nof_sf = row[0];
+  for (int i = 0; i < 5; i++) {
+    sf_config->sf[i] = (uint32_t)row[1 + i];
+  }
+}
+
+int srsran_prach_init(srsran_prach_t* p, uint32_t max_N_ifft_ul)
+{
+  if (p == nullptr || max_N_ifft_ul >= 2049 || max_N_ifft_ul == 0) {
+    fprintf(stderr, "[srsran_prach] Invalid parameters\n");
+    return SRSRAN_ERROR;
+  }
+  memset(p, 0, sizeof(*p));
+  p->max_N_ifft_ul = max_N_ifft_ul;
+  int ndev         = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    fprintf(stderr, "[srsran_prach] no HIP device\n");
+    return SRSRAN_ERROR;
+  }
+  PrachGpu* g = new PrachGpu();
+  p->gpu      = g;
+  // the longest preamble (formats 2 / 3: 2 x 24576 + 21024 T_s) at this symbol size
+  const size_t gen_len = (size_t)SRSRAN_PRACH_MAX_LEN * max_N_ifft_ul / 2048 + 1;
+  if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipMalloc((void**)&g->d_tw_n, max_N_ifft_ul * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_tw_m, (size_t)PRACH_K * max_N_ifft_ul * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_tw839, PRACH_NZC * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_seqs, N_SEQS * PRACH_NZC * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_spec, N_SEQS * PRACH_NZC * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_sig, (size_t)PRACH_K * max_N_ifft_ul * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_gen, gen_len * sizeof(float2)) != hipSuccess || !reserve(g, 16)) {
+    srsran_prach_free(p);
+    return SRSRAN_ERROR;
+  }
+  const std::vector<float2> t = cexp_table(PRACH_NZC, 1.0);
+  if (hipMemcpyAsync(g->d_tw839, t.data(), PRACH_NZC * sizeof(float2), hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+      hipStreamSynchronize(g->stream) != hipSuccess) {
+    srsran_prach_free(p);
+    return SRSRAN_ERROR;
+  }
+  p->max_N_ifft_ul = max_N_ifft_ul;
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_prach_set_cfg(srsran_prach_t* p, srsran_prach_cfg_t* cfg, uint32_t nof_prb)
+{
+  if (p == nullptr || cfg == nullptr || p->gpu == nullptr) {
+    return SRSRAN_ERROR;
+  }
+  const int sz = srsran_symbol_sz(nof_prb);
+  if (sz <= 0 || sz >= 2049 || cfg->config_idx >= 64 || cfg->root_seq_idx >= MAX_ROOTS) {
+    fprintf(stderr, "[srsran_prach] Invalid parameters N_ifft_ul=%d; config_idx=%u; root_seq_idx=%u;\n", sz,
+            cfg->config_idx, cfg->root_seq_idx);
+    return SRSRAN_ERROR;
+  }
+  const uint32_t N_ifft_ul = (uint32_t)sz;
+  if (N_ifft_ul > p->max_N_ifft_ul) {
+    fprintf(stderr,
+            "[srsran_prach] Error in set_cell(): N_ifft_ul (%u) must be lower or equal max_N_ifft_ul (%u) in init()\n",
+            N_ifft_ul, p->max_N_ifft_ul);
+    return SRSRAN_ERROR;
+  }
+  const uint32_t preamble_format = srsran_prach_get_preamble_format(cfg->config_idx);
+  // frame structure type 2 (36.211 Table 5.7.1-3): configurations 48.. are preamble format 4, which config_idx / 16
+  // would take for format 3; frame structure type 1: 48..63 are format 3
+  if (cfg->tdd_config.configured && cfg->config_idx >= 48) {
+    fprintf(stderr, "[srsran_prach] preamble format 4 (TDD config_idx %u) is not provided\n", cfg->config_idx);
+    return SRSRAN_ERROR;
+  }
+  if (cfg->hs_flag) {
+    fprintf(stderr, "[srsran_prach] the high-speed flag (restricted sets) is not provided\n");
+    return SRSRAN_ERROR;
+  }
+  if (cfg->zero_corr_zone >= 16) {
+    fprintf(stderr, "[srsran_prach] Invalid zeroCorrelationZoneConfig=%u\n", cfg->zero_corr_zone);
+    return SRSRAN_ERROR;
+  }
+  if (cfg->enable_successive_cancellation && cfg->zero_corr_zone == 0) {
+    fprintf(stderr, "[srsran_prach] successive cancellation is not provided\n");
+    return SRSRAN_ERROR;
+  }
+  PrachGpu* g = (PrachGpu*)p->gpu;
+  int       radix[OFDM_MAX_STAGES];
+  if (ofdm_plan(N_ifft_ul, radix) <= 0) {
+    fprintf(stderr, "[srsran_prach] unsupported symbol size %u\n", N_ifft_ul);
+    return SRSRAN_ERROR;
+  }
+  p->is_nr                   = cfg->is_nr;
+  p->config_idx              = cfg->config_idx;
+  p->f                       = preamble_format;
+  p->rsi                     = cfg->root_seq_idx;
+  p->hs                      = false;
+  p->zczc                    = cfg->zero_corr_zone;
+  p->detect_factor           = DETECT_FACTOR;
+  p->num_ra_preambles        = cfg->num_ra_preambles;
+  p->successive_cancellation = false;  // any zone but 0: switched off as prach.c:644-647
+  p->freq_domain_offset_calc = cfg->enable_freq_domain_offset_calc;
+  p->tdd_config              = cfg->tdd_config;
+  p->N_zc                    = SRSRAN_PRACH_N_ZC_LONG;
+  p->N_cs                    = kPrachNcs[p->zczc];
+  gen_seqs(p);
+  if (p->num_ra_preambles < 4 || p->num_ra_preambles > p->N_roots) {
+    p->num_ra_preambles = p->N_roots;
+  }
+  p->N_ifft_ul    = N_ifft_ul;
+  p->N_ifft_prach = p->N_ifft_ul * DELTA_F / DELTA_F_RA;
+  p->deadzone     = 0;
+  p->N_seq        = kPrachTseq[p->f] * p->N_ifft_ul / 2048;
+  p->N_cp         = kPrachTcp[p->f] * p->N_ifft_ul / 2048;
+  p->T_seq        = kPrachTseq[p->f] * LTE_TS;
+  p->T_tot        = (kPrachTseq[p->f] + kPrachTcp[p->f]) * LTE_TS;
+  g->metrics.valid = false;
+
+  hipStreamSynchronize(g->stream);  // nothing of an earlier call reads the tables any more
+  bool ok = true;
+  if (g->tw_N != N_ifft_ul) {
+    const std::vector<float2> tn = cexp_table(N_ifft_ul, -1.0), tm = cexp_table(p->N_ifft_prach, -1.0);
+    ok = hipMemcpyAsync(g->d_tw_n, tn.data(), tn.size() * sizeof(float2), hipMemcpyHostToDevice, g->stream) == hipSuccess &&
+         hipMemcpyAsync(g->d_tw_m, tm.data(), tm.size() * sizeof(float2), hipMemcpyHostToDevice, g->stream) == hipSuccess &&
+         hipStreamSynchronize(g->stream) == hipSuccess;  // the host vectors go out of scope
+    g->tw_N = ok ? N_ifft_ul : 0;
+  }
+  fill_fft(g, N_ifft_ul);
+  ok = ok &&
+       hipMemcpyAsync(g->d_seqs, p->seqs, N_SEQS * PRACH_NZC * sizeof(float2), hipMemcpyHostToDevice, g->stream) == hipSuccess &&
+       prach_seq_dft_launch(g->d_seqs, g->d_tw839, g->d_spec, N_SEQS, g->stream) == hipSuccess &&
+       hipStreamSynchronize(g->stream) == hipSuccess;
+  if (!ok) {
+    fprintf(stderr, "[srsran_prach] set_cfg: %s\n", hipGetErrorString(hipGetLastError()));
+    p->N_ifft_prach = 0;
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_prach_gpu_gen(srsran_prach_t* p, uint32_t seq_index, uint32_t freq_offset, cf_t* d_signal)
+{
+  if (p == nullptr || p->gpu == nullptr || seq_index >= N_SEQS || d_signal == nullptr || p->N_ifft_prach == 0) {
+    return SRSRAN_ERROR;
+  }
+  PrachGpu* g = (PrachGpu*)p->gpu;
+  if (gen_device(p, seq_index, freq_offset, (float2*)d_signal) != SRSRAN_SUCCESS ||
+      hipStreamSynchronize(g->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_prach_gen(srsran_prach_t* p, uint32_t seq_index, uint32_t freq_offset, cf_t* signal)
+{
+  if (p == nullptr || p->gpu == nullptr || seq_index >= N_SEQS || signal == nullptr || p->N_ifft_prach == 0) {
+    return SRSRAN_ERROR;
+  }
+  PrachGpu* g = (PrachGpu*)p->gpu;
+  if (gen_device(p, seq_index, freq_offset, g->d_gen) != SRSRAN_SUCCESS ||
+      hipMemcpyAsync(signal, g->d_gen, (size_t)(p->N_cp + p->N_seq) * sizeof(float2), hipMemcpyDeviceToHost,
+                     g->stream) != hipSuccess ||
+      hipStreamSynchronize(g->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+void srsran_prach_set_detect_factor(srsran_prach_t* p, float factor)
+{
+  p->detect_factor = factor;
+}
+
+int srsran_prach_detect(srsran_prach_t* p,
+                        uint32_t        freq_offset,
+                        cf_t*           signal,
+                        uint32_t        sig_len,
+                        uint32_t*       indices,
+                        uint32_t*       n_indices)
+{
+  return srsran_prach_detect_offset(p, freq_offset, signal, sig_len, indices, nullptr, nullptr, n_indices);
+}
+
+int srsran_prach_detect_offset(srsran_prach_t* p,
+                               uint32_t        freq_offset,
+                               cf_t*           signal,
+                               uint32_t        sig_len,
+                               uint32_t*       indices,
+                               float*          t_offsets,
+                               float*          peak_to_avg,
+                               uint32_t*       n_indices)
+{
+  if (indices == nullptr || n_indices == nullptr) {
+    return SRSRAN_ERROR;
+  }
+  uint32_t  b0  = 0;
+  const int chk = check_occ(p, signal, sig_len, freq_offset, &b0);
+  if (chk != SRSRAN_SUCCESS) {
+    return chk;
+  }
+  PrachGpu* g = (PrachGpu*)p->gpu;
+  if (hipMemcpyAsync(g->d_sig, signal, (size_t)p->N_ifft_prach * sizeof(float2), hipMemcpyHostToDevice, g->stream) !=
+      hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  srsran_prach_gpu_occ_t occ = {p, freq_offset, (const cf_t*)g->d_sig, sig_len};
+  static thread_local srsran_prach_gpu_res_t res;
+  if (detect_core(1, &occ, &b0, &res) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR;
+  }
+  *n_indices = res.nof_det;
+  memcpy(indices, res.indices, res.nof_det * sizeof(uint32_t));
+  if (t_offsets) {
+    memcpy(t_offsets, res.t_offsets, res.nof_det * sizeof(float));
+  }
+  if (peak_to_avg) {
+    memcpy(peak_to_avg, res.peak_to_avg, res.nof_det * sizeof(float));
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_prach_gpu_detect_batch(uint32_t nof_occ, const srsran_prach_gpu_occ_t* occ, srsran_prach_gpu_res_t* res)
+{
+  if (nof_occ == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (occ == nullptr || res == nullptr) {
+    return SRSRAN_ERROR;
+  }
+  std::vector<uint32_t> b0(nof_occ);
+  for (uint32_t i = 0; i < nof_occ; i++) {
+    const int chk = check_occ(occ[i].prach, occ[i].d_signal, occ[i].sig_len, occ[i].freq_offset, &b0[i]);
+    if (chk != SRSRAN_SUCCESS) {
+      return chk;
+    }
+  }
+  return detect_core(nof_occ, occ, b0.data(), res);
+}
+
+int srsran_prach_gpu_get_metrics(srsran_prach_t* p, float* ratio, uint32_t* offset, uint32_t* nof_roots, uint32_t* nof_wins)
+{
+  if (p == nullptr || p->gpu == nullptr || !((PrachGpu*)p->gpu)->metrics.valid) {
+    return SRSRAN_ERROR;
+  }
+  const Metrics& m = ((PrachGpu*)p->gpu)->metrics;
+  uint32_t       n = m.nof_roots * m.nof_wins;
+  n                = n > PRACH_MAX_WIN ? PRACH_MAX_WIN : n;
+  if (ratio) {
+    memcpy(ratio, m.ratio, n * sizeof(float));
+  }
+  if (offset) {
+    memcpy(offset, m.offset, n * sizeof(uint32_t));
+  }
+  if (nof_roots) {
+    *nof_roots = m.nof_roots;
+  }
+  if (nof_wins) {
+    *nof_wins = m.nof_wins;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_prach_gpu_detect_time(srsran_prach_t* p, bool enable, float* device_us)
+{
+  if (p == nullptr || p->gpu == nullptr) {
+    return SRSRAN_ERROR;
+  }
+  PrachGpu* g = (PrachGpu*)p->gpu;
+  if (device_us) {
+    *device_us = g->last_us;
+  }
+  if (enable && (!g->ev0 || !g->ev1) &&
+      (hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess)) {
+    return SRSRAN_ERROR;
+  }
+  g->timing = enable;
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_prach_free(srsran_prach_t* p)
+{
+  if (p == nullptr) {
+    return SRSRAN_ERROR;
+  }
+  PrachGpu* g = (PrachGpu*)p->gpu;
+  if (g) {
+    if (g->stream) {
+      hipStreamSynchronize(g->stream);
+    }
+    release_batch(g);
+    if (g->ev0) {
+      hipEventDestroy(g->ev0);
+    }
+    if (g->ev1) {
+      hipEventDestroy(g->ev1);
+    }
+    hipFree(g->d_tw_n);
+    hipFree(g->d_tw_m);
+    hipFree(g->d_tw839);
+    hipFree(g->d_seqs);
+    hipFree(g->d_spec);
+    hipFree(g->d_sig);
+    hipFree(g->d_gen);
+    if (g->stream) {
+      hipStreamDestroy(g->stream);
+    }
+    delete g;
+  }
+  memset(p, 0, sizeof(*p));
+  return 0;
+}
+
+}  // extern "C"

@@ -229,8 +229,9 @@ __host__ __device__ __forceinline__ Geo geo(int K, int Ls, int M, bool slot)
 }
 
 struct Raw {
-  uint32_t a[W];  // systematic LLR (DEC1) / slot of pi(position) (DEC2)
-  uint32_t b[W];  // parity0 / parity1
+  uint32_t a[W];     // systematic LLR (DEC1)
+  uint16_t slot[W];  // slot of pi(position) (DEC2): widened where it is used, after the wait for it
+  uint32_t b[W];     // parity0 / parity1
 };
 
 typedef short __attribute__((address_space(3)))* lshort;
@@ -278,13 +279,18 @@ __device__ __forceinline__ void issue(const Lane& c, Raw& r, int t0)
 #ifdef TDECS_FAKELOAD  // diagnostic timing build only: no global loads (results are garbage)
 #pragma unroll
   for (int i = 0; i < W; i++) {
-    r.a[i] = D2 ? (uint32_t)((c.s * 37 + t0 + i) & 511) : (soff + i) & 0xff;  // slots < 512 <= K
+    r.a[i]    = (soff + i) & 0xff;
+    r.slot[i] = (uint16_t)((c.s * 37 + t0 + i) & 511);  // slots < 512 <= K
     r.b[i] = (poff + 3 * i) & 0xff;
   }
 #else
 #pragma unroll
   for (int i = 0; i < W; i++) {
-    r.a[i] = D2 ? ldb(c.rtf, 2u * (uint32_t)c.s, soff, ROWB * i) : ldb(c.rin, c.voff, soff, ROWB * i);
+    if (D2) {
+      r.slot[i] = (uint16_t)ldb(c.rtf, 2u * (uint32_t)c.s, soff, ROWB * i);
+    } else {
+      r.a[i] = ldb(c.rin, c.voff, soff, ROWB * i);
+    }
     r.b[i] = ldb(c.rin, c.voff, poff, ROWB * i);
   }
 #endif
@@ -420,60 +426,101 @@ __device__ __forceinline__ St beta_window(const Lane& c, St P, int t0, bool stor
   return P;
 }
 
+// One full wait instead of the compiler's counted wait per value: what is waited for was issued a whole window
+// earlier.  s_waitcnt immediates (gfx9 encoding): vmcnt(0) / lgkmcnt(0) with the other counters left at their maximum.
+// The scheduling barriers keep the consumers below the wait (the scheduler moves register-only work across it).
+template <int IMM>
+__device__ __forceinline__ void wait_for()
+{
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt(IMM);
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void wait_vm0() { wait_for<0x0f70>(); }
+__device__ __forceinline__ void wait_lgkm0() { wait_for<0xc07f>(); }
+__device__ __forceinline__ void wait_all0() { wait_for<0x0070>(); }
+
+// LDS address of S[slot]: base + 2 * the low half of the loaded register, in one instruction (the compiler widens
+// the 16-bit value with a mask of its own otherwise; a 16-bit float operand is handed over as loaded).  Register-only.
+__device__ __forceinline__ uint32_t slot_addr(lshort S, uint16_t slot)
+{
+  uint32_t a;
+  asm("v_mad_u32_u16 %0, %1, 2, %2" : "=v"(a) : "v"(__builtin_bit_cast(_Float16, slot)), "v"((uint32_t)(size_t)S));
+  return a;
+}
+
 // Window inputs of one side, prefetched along the side's window sequence (as tdec16_kernel.hip):
 //   alpha side: training [L-40, L-24), [L-24, L-8), [L-8, L); then windows 0, 1, ..., Ma-1
 //   beta side:  training [32, 40), [16, 32), [0, 16);       then windows Ma-1, ..., 1, 0
+// The caller walks the sequence: next() hands out the window loaded before and prefetches the one at tnext,
+// unconditionally (past the last window of a loop the caller repeats a window of the sequence; never used);
+// taken() closes a window.
 template <bool D2>
 struct Pipe {
   Raw      g;
-  uint32_t dv[W];
-  int      nwin, Ma;
-  bool     beta;
+  uint32_t dv[W];  // DEC1: the a-priori values of the window in flight; DEC2: the LDS addresses of its slots (taken)
 
-  __device__ __forceinline__ int t0_of(int idx, int L) const
-  {
-    if (beta) {
-      return idx < NTR ? (NTR - 1 - idx) * W : (Ma - 1 - (idx - NTR)) * W;
-    }
-    return idx < NTR ? L - OVL + W * idx : (idx - NTR) * W;
-  }
+  // (lo, hi) halves of two loaded values in one register: a v_perm_b32 that ignores their upper halves
+  static __device__ __forceinline__ v2s pack(uint32_t lo, uint32_t hi) { return v2s{(short)lo, (short)hi}; }
 
-  __device__ __forceinline__ void load(const Lane& c, int idx)
+  __device__ __forceinline__ void load(const Lane& c, int t0)
   {
-    if (idx < nwin) {
-      const int t0 = t0_of(idx, c.L);
-      issue<D2>(c, g, t0);
-      if (!D2) {
+    issue<D2>(c, g, t0);
+    if (!D2) {
 #pragma unroll
-        for (int i = 0; i < W; i++) {
-          dv[i] = (uint16_t)c.Ssb[t0 + i];
-        }
+      for (int i = 0; i < W; i++) {
+        dv[i] = (uint16_t)c.Ssb[t0 + i];
       }
     }
   }
-  __device__ __forceinline__ void start(const Lane& c) { load(c, 0); }
-  __device__ __forceinline__ void next(const Lane& c, int idx, uint32_t* xw, uint32_t* aux)
+  // after the last step of a window: the loads issued at its start have landed (one wait); DEC2 turns the slots
+  // into LDS addresses here, so that the registers the next loads fill are free
+  __device__ __forceinline__ void taken(const Lane& c)
   {
     if (D2) {
-      uint32_t d[W], hi[W];
+      wait_vm0();
 #pragma unroll
       for (int i = 0; i < W; i++) {
-        aux[i] = (uint32_t)(size_t)(c.S + g.a[i]);
-        d[i]   = (uint16_t)*(lshort)(size_t)aux[i];
-        hi[i]  = g.b[i] << 16;
+        dv[i] = slot_addr(c.S, g.slot[i]);
       }
-      load(c, idx + 1);
+    }
+  }
+  __device__ __forceinline__ void start(const Lane& c, int t0)
+  {
+    load(c, t0);
+    taken(c);
+  }
+  template <bool LAST = false>
+  __device__ __forceinline__ void next(const Lane& c, int tnext, uint32_t* xw, uint32_t* aux)
+  {
+    if (D2) {
+      short    d[W];
+      uint32_t pb[W];
 #pragma unroll
       for (int i = 0; i < W; i++) {
-        xw[i] = pin(hi[i] | d[i]);
+        aux[i] = dv[i];
+        d[i]   = *(lshort)(size_t)aux[i];
+        pb[i]  = g.b[i];
+      }
+      if (!LAST) {
+        issue<D2>(c, g, tnext);
+      }
+      wait_lgkm0();
+#pragma unroll
+      for (int i = 0; i < W; i++) {
+        xw[i] = pin(v2u(pack((uint16_t)d[i], pb[i])));
       }
     } else {
+      wait_all0();
 #pragma unroll
       for (int i = 0; i < W; i++) {
-        xw[i]  = pin(v2u(padd(u2v(__builtin_amdgcn_perm(g.b[i], g.a[i], 0x05040100u)), u2v(dv[i]))));
+        xw[i]  = pin(v2u(padd(pack(g.a[i], g.b[i]), u2v(dv[i]))));
         aux[i] = dv[i];
       }
-      load(c, idx + 1);
+      __builtin_amdgcn_sched_barrier(0);  // the consumed registers are free before the loads that refill them
+      if (!LAST) {
+        load(c, tnext);
+      }
     }
   }
 };
@@ -494,27 +541,25 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
   const int L     = c.L;
   const int Mfull = L / W;
   const int Ma    = (L + W - 1) / W;
-  const int h     = max(1, min((L + W) / (2 * W), L / W));
+  const int h     = max(1, min((L + 2 * W - 1) / (2 * W), L / W));
   Pipe<D2>  pp;
-  pp.nwin = NTR + Ma;
-  pp.Ma   = Ma;
-  pp.beta = __builtin_amdgcn_readfirstlane(wave) != 0;
-  uint32_t xw[W];
-  uint32_t aux[W];
-  pp.start(c);
+  uint32_t  xw[W];
+  uint32_t  aux[W];
   if (wave == 0) {
+    pp.start(c, L - OVL);
     // ================= alpha side =================
     St P = neg_state();
     TDECS_STAMP(st0);
     // training over the last 40 steps of the own sub-block (win.h:747-756)
 #pragma unroll
     for (int w = 0; w < NTR; w++) {
-      pp.next(c, w, xw, aux);
+      pp.next(c, w < NTR - 1 ? L - OVL + W * (w + 1) : 0, xw, aux);
 #pragma unroll
       for (int i = 0; i < (W < OVL - w * W ? W : OVL - w * W); i++) {
         P = step<false>(P, xw[i]);
         if (norm_at(w * W + i)) P = norm(P);
       }
+      pp.taken(c);
     }
     TDECS_STAMP(st0 + 1);
     {  // move_left: sub-block s starts from the training state of s - 1; s = 0 is known
@@ -529,42 +574,47 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
 #pragma unroll 1
     for (int ma = 0; ma < h; ma++) {
       const int t0 = ma * W;
-      pp.next(c, NTR + ma, xw, aux);
+      pp.next(c, t0 + W, xw, aux);  // h < Ma: window h exists
       ck_put(c, ma, P);
 #pragma unroll
       for (int i = 0; i < W; i++) {
         P = step<false>(P, xw[i]);
         if (nrm(t0, i)) P = norm(P);
       }
+      pp.taken(c);
     }
     TDECS_STAMP(st0 + 2);
     __syncthreads();
     TDECS_STAMP(st0 + 3);
     // phase 2: windows [h, Ma): beta recomputed from the checkpoint above the window, then alpha + LLR
+    const int tlast = (Ma - 1) * W;
 #pragma unroll 1
     for (int ma = h; ma < Mfull; ma++) {
-      pp.next(c, NTR + ma, xw, aux);
+      pp.next(c, min(ma * W + W, tlast), xw, aux);
       P = alpha_llr_window<D2, BITS, true>(c, P, ma * W, ck_get(c, ma), xw, aux);
+      pp.taken(c);
     }
     if (Ma > Mfull) {
-      pp.next(c, NTR + Mfull, xw, aux);
+      pp.template next<true>(c, 0, xw, aux);
       alpha_llr_window<D2, BITS, false>(c, P, Mfull * W, ck_get(c, Mfull), xw, aux);
     }
     TDECS_STAMP(st0 + 4);
   } else {
     // ================= beta side =================
+    pp.start(c, (NTR - 1) * W);
     St P = neg_state();
     TDECS_STAMP(st0);
     // training over the first 40 steps of the own sub-block, backwards (win.h:622-630)
 #pragma unroll
     for (int w = 0; w < NTR; w++) {  // the top (maybe partial) training window first
-      pp.next(c, w, xw, aux);
       const int t0 = (NTR - 1 - w) * W;
+      pp.next(c, w < NTR - 1 ? t0 - W : (Ma - 1) * W, xw, aux);
 #pragma unroll
       for (int i = (W < OVL - t0 ? W : OVL - t0) - 1; i >= 0; i--) {
         P = step<true>(P, xw[i]);
         if (norm_at(t0 + i)) P = norm(P);
       }
+      pp.taken(c);
     }
     TDECS_STAMP(st0 + 1);
     {  // move_right: sub-block s starts from the training state of s + 1; the last from the tail
@@ -591,13 +641,15 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
     St Bst = P;  // stored (pre-normalisation) beta of the position above the current window
     // phase 1: windows [h, Ma) from the top (the top one maybe partial)
     if (Ma > Mfull) {
-      pp.next(c, NTR, xw, aux);
+      pp.next(c, (mtop - 1) * W, xw, aux);  // Ma >= 4
       P = beta_window<false>(c, P, mtop * W, mtop > h, Bst, xw);
+      pp.taken(c);
     }
 #pragma unroll 1
     for (int mb = Mfull - 1; mb >= h; mb--) {
-      pp.next(c, NTR + mtop - mb, xw, aux);
+      pp.next(c, mb * W - W, xw, aux);  // mb >= h >= 1
       P = beta_window<true>(c, P, mb * W, mb > h, Bst, xw);
+      pp.taken(c);
     }
     TDECS_STAMP(st0 + 2);
     __syncthreads();
@@ -607,7 +659,7 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
 #pragma unroll 1
     for (int mb = h - 1; mb >= 0; mb--) {
       const int t0 = mb * W;
-      pp.next(c, NTR + mtop - mb, xw, aux);
+      pp.next(c, max(t0 - W, 0), xw, aux);
       St Pa = ck_get(c, mb);
       St aw[W];  // alpha entering each position (candidates rebuilt at LLR time)
 #pragma unroll
@@ -630,6 +682,7 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
       if (BITS == 2 && !D2) {
         flush_bits(c, t0, wbits);
       }
+      pp.taken(c);
     }
     TDECS_STAMP(st0 + 4);
   }

@@ -46,7 +46,7 @@ def main():
     W = 8 if K <= a.w8 else 16
     L = K // nsb
     Ma = (L + W - 1) // W
-    h = max(1, min((L + W) // (2 * W), L // W))
+    h = max(1, min((L + 2 * W - 1) // (2 * W), L // W))
     rng = np.random.default_rng(3)
     _, llr = SY.make_llrs(K, 4.0, rng, 8)
     sb = SY.natural_to_sb(K, llr)

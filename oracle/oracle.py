@@ -252,6 +252,26 @@ class Oracle(_Lib, _PhyMixin):
                   sync_error=float(out[4]))
         return ce, st, grids, ns
 
+    def chest_dl_ext_tdd(self, grids, nof_prb, cell_id, nports, sf_idx, symbol_sz, cp=0, estimator=0, noise_alg=0,
+                         filt_order=4, filt_std=1.0, sync=False, noise_state=None, nsym=(4, 2)):
+        """oracle_chest_dl_ext_tdd: chest_dl_ext with a Gauss filter of integer order (0 = automatic)"""
+        grids = np.array(grids, np.complex64, copy=True)
+        nrx, n = grids.shape
+        ce = np.zeros((nports, nrx, n), np.complex64)
+        out = np.zeros(5, np.float32)
+        ns = np.zeros((4, 4), np.float32) if noise_state is None else np.array(noise_state, np.float32, copy=True)
+        pss = np.zeros(62, np.complex64)
+        self.lib.oracle_pss_generate.argtypes = [ctypes.c_uint32, ctypes.c_void_p]
+        self.lib.oracle_pss_generate(cell_id % 3, pss.ctypes.data)
+        f = self.lib.oracle_chest_dl_ext_tdd
+        f.argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * 10 + [ctypes.c_float, ctypes.c_uint32] + \
+            [ctypes.c_void_p] * 2 + [ctypes.c_uint32] * 2 + [ctypes.c_void_p] * 2
+        f(grids.ctypes.data, nof_prb, cell_id, nports, nrx, sf_idx, symbol_sz, cp, estimator, noise_alg, int(filt_order),
+          filt_std, 1 if sync else 0, pss.ctypes.data, ns.ctypes.data, nsym[0], nsym[1], ce.ctypes.data, out.ctypes.data)
+        st = dict(noise=float(out[0]), rsrp=float(out[1]), rssi=float(out[2]), cfo=float(out[3]),
+                  sync_error=float(out[4]))
+        return ce, st, grids, ns
+
     def mbsfn_pilots(self, nof_prb, area, sf):
         """srsran_refsignal_mbsfn_gen_seq's pilots of subframe sf: (3, 6 N_RB) complex64"""
         out = np.zeros(18 * nof_prb, np.complex64)

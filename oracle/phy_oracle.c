@@ -619,7 +619,8 @@ void oracle_csi_correction_b(int mod, const float* csi, int8_t* e, uint32_t nof_
 /* ======================= DL channel estimation (chest_dl.c, refsignal_dl.c) =======================
  * srsUE default configuration (srsue/src/phy/phy_common.cc:83-107, main.cc defaults): estimator
  * AVERAGE, Gauss smoothing filter order 4 / stddev 1.0, noise algorithm REFS, normal subframe,
- * normal or extended CP, FDD.  Restated (chest_dl.c and refsignal_dl.c include the generated srsran.h):
+ * normal or extended CP, FDD.  Restated (chest_dl.c and refsignal_dl.c are not part of _ref), and pinned to recorded
+ * results of the compiled chest_dl.c by tests/test_chest_golden.py:
  *   CRS             srsran_refsignal_cs_set_cell  refsignal_dl.c:65-119, fidx/nsymbol 249-266
  *   LS              estimate_port                 chest_dl.c:806-834
  *   noise (REFS)    estimate_noise_pilots         chest_dl.c:325-400
@@ -853,7 +854,9 @@ static int chest_dl_impl(const float* grid, uint32_t nof_prb, uint32_t cell_id, 
         }
       }
       rssi[rx][port] = rs / (float)nsym;
-      if (nsym == 4) { /* chest_estimate_cfo (port-0 geometry), kept from the last port processed */
+      if (nsym == 4) { /* chest_estimate_cfo (port-0 geometry) of the last port with 4 CRS symbols.  The reference
+                        * runs it for ports 2 / 3 too, on their 2 rows and 2 stale rows of port 1 (chest_dl.c:655):
+                        * in 4-port cells its q->cfo is that product; this is the library's documented deviation */
         cpx sum = {0, 0};
         for (uint32_t i = 0; i < 2; i++) {
           for (uint32_t k = 0; k < np / 4; k++) {
@@ -1158,7 +1161,7 @@ int oracle_chest_dl_ext_f(float* grid, uint32_t nof_prb, uint32_t cell_id, uint3
         }
       }
       rssi[rx][port] = rs / (float)nsym;
-      if (nsym == 4) {
+      if (nsym == 4) { /* ports 0 / 1 only: not the reference's value in 4-port cells, see chest_dl_impl */
         cpx sum = {0, 0};
         for (uint32_t i = 0; i < 2; i++) {
           for (uint32_t k = 0; k < np / 4; k++) {

@@ -573,7 +573,10 @@ static void fill_res(srsran_chest_dl_t* q, const float* st, srsran_chest_dl_res_
     }
     n += s / (float)np;
   }
-  // chest_estimate_cfo: the last (rx, port) pair with 4 CRS symbols wins (chest_dl.c:655)
+  // chest_estimate_cfo of the last (rx, port) pair with 4 CRS symbols, i.e. port 0 / 1 of the last antenna.  A
+  // deviation in 4-port cells: the reference runs it for every port (chest_dl.c:655) and for ports 2 / 3 it pairs
+  // their two rows of LS estimates with rows 2 / 3 of the buffer, which still hold port 1's -- its q->cfo there is
+  // that product, not a frequency estimate (finding 8; the fixtures keep it as `cfo`)
   for (int idx = (int)(nrx * np) - 1; update_cfo && idx >= 0; idx--) {
     const uint32_t p = (uint32_t)idx % np;
     if (p < 2) {

@@ -1,6 +1,8 @@
 """GPU parity of the DL CRS channel estimator (srsUE default configuration) against the oracle
-(oracle/phy_oracle.c, a restatement of chest_dl.c / refsignal_dl.c whose buildable pieces --
-Gauss filter, conv_same, Gold sequence -- are pinned to the reference in test_phy_oracle.py).
+(oracle/phy_oracle.c, a restatement of chest_dl.c / refsignal_dl.c: its pieces -- Gauss filter,
+conv_same, Gold sequence -- are pinned to the reference in test_phy_oracle.py, its composition to
+recorded results of the compiled chest_dl.c in test_chest_golden.py; test_chest_ref_gpu.py compares
+the GPU with those records directly).
 Estimates are compared at float tolerance (the reductions sum in a different order)."""
 import numpy as np
 import pytest

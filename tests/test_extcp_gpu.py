@@ -3,7 +3,8 @@
 demodulator against numpy, the CRS estimator against the oracle (phy_oracle.c), srsran_pdsch_decode
 bit-exact against the oracle chain (oracle/pdsch_chain.py, cp=1), the UE DL batch against the
 host-synchronous path, and the GPU eNB transmitter against the CPU transmitter (synth/synth.py).
-Parity is anchored as for normal CP: the pieces the oracle restates are pinned in test_phy_oracle.py;
+Parity is anchored as for normal CP: the pieces the oracle restates are pinned in test_phy_oracle.py, the estimator's
+composition to recorded results of the compiled chest_dl.c with extended CP (test_chest_golden.py);
 the extended-CP RE map and grant size rest on two independent restatements (test_pdsch_map.py)."""
 import numpy as np
 import pytest

@@ -12,8 +12,8 @@ ofdm.c:522-578; chest_dl.c:263-278, 437-600, 836-865; refsignal_dl.c:316-502).
   the MBSFN reference signals and PMCH symbols, through a channel: srsran_ue_dl_decode_fft_estimate finds the CFI
   and srsran_ue_dl_find_dl_dci / _find_ul_dci the DCIs, with the grid and estimate equal to the oracle's on the
   same samples.  As in the reference, only antenna 0 is transformed (the other antennas keep the previous grid).
-The MBSFN reference-signal expressions are restatements (refsignal_dl.c does not build here): parity unpinned for
-their composition, as for the CRS estimator's."""
+The MBSFN reference-signal expressions and the estimator's MBSFN path are restatements, pinned to recorded results of
+the compiled refsignal_dl.c / chest_dl.c (test_chest_golden.py, the m6 / m15 cases)."""
 import numpy as np
 import pytest
 import torch

@@ -3,7 +3,8 @@ pdsch.c:90-107, 154-159; refsignal_dl.c:169-226).
 
 * the CRS estimator in special subframes, whose DwPTS holds 1-4 CRS symbols a port (the 1- / 2-symbol noise path,
   the time average over the symbols present, the one-symbol interpolation), host-synchronous and batched, against
-  the oracle restatement (oracle_chest_dl_tdd / _ext_tdd) at 2e-5 of the largest estimate;
+  the oracle restatement (oracle_chest_dl_tdd / _ext_tdd; itself pinned to recorded results of the compiled
+  chest_dl.c in special subframes with 1 / 3 / 4 CRS symbols, test_chest_golden.py) at 2e-5 of the largest estimate;
 * the whole UE DL chain on TDD cells from time samples (synth/ TDD transmitter: SSS in the last symbol of
   subframes 0 / 5, PSS in symbol 2 of subframes 1 / 6, special subframes sending their DwPTS only): every
   downlink and special subframe of a frame decoded host-synchronously and in one batch, equal to the oracle chain

@@ -143,6 +143,16 @@ int srsran_pusch_decode(srsran_pusch_t*        q,
                         cf_t*                  sf_symbols,
                         srsran_pusch_res_t*    out);
 
+/* added, read-only: the soft values of the last srsran_pusch_decode on this object, for checking them against a
+ * reference.  *d_sym: nof_re de-precoded symbols (pusch.c:416's q->d); *d_llr: nof_bits descrambled LLRs as
+ * srsran_ulsch_decode left them (the HARQ-ACK positions are zeroed in place, as sch.c does).  Device pointers, valid
+ * until the next decode on the object; SRSRAN_ERROR before the first decode and after a srsran_pusch_gpu_decode_batch. */
+int srsran_pusch_gpu_last_soft(srsran_pusch_t* q,
+                               const cf_t**    d_sym,
+                               uint32_t*       nof_sym,
+                               const int16_t** d_llr,
+                               uint32_t*       nof_llr);
+
 /* ---- added: many UEs of one or more cells in a few launches ----
  * Per entry: the device subframe grid of its cell, the PUSCH configuration (UCI included) and the
  * cell's chest object (pregenerated DMRS).  Runs chest_ul_estimate_pusch + pusch_decode for all

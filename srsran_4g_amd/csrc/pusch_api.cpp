@@ -296,6 +296,7 @@ struct PuschGpu {
   size_t      g_cap  = 0;
   uint8_t*    d_data = nullptr;  // batch: decoded TBs of the UEs without UCI
   size_t      data_cap = 0;
+  uint32_t    last_nsym = 0, last_nllr = 0;  // the last host-sync decode's counts (srsran_pusch_gpu_last_soft)
 };
 
 uint32_t pusch_seed(uint16_t rnti, uint32_t nslot, uint32_t cell_id)  // sequences.c:119-122
@@ -715,6 +716,7 @@ int srsran_pusch_decode(srsran_pusch_t*        q,
     fprintf(stderr, "[srsran_pusch] the 8-bit LLR path is not provided\n");
     return SRSRAN_ERROR;
   }
+  ((PuschGpu*)q->gpu)->last_nsym = ((PuschGpu*)q->gpu)->last_nllr = 0;  // set again when this decode has run
   limit_64qam(cfg);
   const uint32_t L = cfg->grant.L_prb, M = L * SRSRAN_NRE;
   if (check_alloc(q->cell, cfg) != SRSRAN_SUCCESS) {
@@ -796,6 +798,25 @@ int srsran_pusch_decode(srsran_pusch_t*        q,
   out->crc                  = ret == 0;
   out->avg_iterations_block = q->ul_sch.avg_iterations;
   cfg->last_O_cqi           = (uint32_t)srsran_cqi_size(&cfg->uci_cfg.cqi);
+  g->last_nsym              = cfg->grant.nof_re;
+  g->last_nllr              = nb;
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_pusch_gpu_last_soft(srsran_pusch_t* q, const cf_t** d_sym, uint32_t* nof_sym, const int16_t** d_llr,
+                               uint32_t* nof_llr)
+{
+  if (!q || !q->gpu || !d_sym || !nof_sym || !d_llr || !nof_llr) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  PuschGpu* g = (PuschGpu*)q->gpu;
+  if (g->last_nsym == 0) {  // no host-sync decode yet, or a batch has reused the buffers since
+    return SRSRAN_ERROR;
+  }
+  *d_sym   = (const cf_t*)g->d_sym;
+  *nof_sym = g->last_nsym;
+  *d_llr   = g->d_q;
+  *nof_llr = g->last_nllr;
   return SRSRAN_SUCCESS;
 }
 
@@ -816,6 +837,7 @@ int srsran_pusch_gpu_decode_batch(srsran_pusch_t*              q,
   }
   PuschGpu*   g  = (PuschGpu*)q->gpu;
   hipStream_t st = sch_stream(&q->ul_sch);
+  g->last_nsym = g->last_nllr = 0;  // the symbol / LLR buffers are laid out per UE from here on
 
   // ---- host: descriptors and the device layout of every UE's buffers ----
   std::vector<PuschUe> desc(nof_ue);

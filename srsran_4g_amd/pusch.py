@@ -82,6 +82,8 @@ def lib():
             "srsran_pusch_set_cell": ([PU, srsran_cell_t], ctypes.c_int),
             "srsran_pusch_assert_grant": ([ctypes.c_void_p], ctypes.c_int),
             "srsran_pusch_decode": ([PU, SF, CFG, RES, _cfp, ctypes.POINTER(srsran_pusch_res_t)], ctypes.c_int),
+            "srsran_pusch_gpu_last_soft": ([PU, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32),
+                                            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u32)], ctypes.c_int),
             "srsran_pusch_gpu_decode_batch": ([PU, u32, ctypes.POINTER(srsran_pusch_gpu_ue_t), RES,
                                                ctypes.POINTER(srsran_pusch_res_t)], ctypes.c_int),
         }
@@ -148,6 +150,25 @@ class Pusch:
         ret = lib().srsran_pusch_decode(ctypes.byref(self.q), ctypes.byref(sf), ctypes.byref(cfg),
                                         ctypes.byref(chest_res), g.ctypes.data, ctypes.byref(out))
         return ret, out, data
+
+    def last_soft(self):
+        """srsran_pusch_gpu_last_soft: (device pointer, count) of the de-precoded symbols and of the LLRs"""
+        ds, dq, ns, nq = ctypes.c_void_p(), ctypes.c_void_p(), u32(), u32()
+        if lib().srsran_pusch_gpu_last_soft(ctypes.byref(self.q), ctypes.byref(ds), ctypes.byref(ns), ctypes.byref(dq),
+                                            ctypes.byref(nq)):
+            raise RuntimeError("srsran_pusch_gpu_last_soft: no host-sync decode to read")
+        return (ds.value, ns.value), (dq.value, nq.value)
+
+    def read_soft(self):
+        """host copies of last_soft(): (complex64 symbols, int16 LLRs) (test helper)"""
+        import torch  # device copies go through torch's HIP runtime
+
+        from .sch import _memcpy_d2h
+        (ds, ns), (dq, nq) = self.last_soft()
+        sym, llr = torch.empty(2 * ns, dtype=torch.float32), torch.empty(nq, dtype=torch.int16)
+        _memcpy_d2h(sym, ds, 8 * ns)
+        _memcpy_d2h(llr, dq, 2 * nq)
+        return sym.numpy().view(np.complex64), llr.numpy()
 
     def free(self):
         if self.q.gpu:

@@ -4,7 +4,9 @@ demapper / descrambler / uci.c / decode_tb):
   srsran_dft_precoding_gpu   every valid L_prb (1..100) against numpy's inverse FFT x sqrt(M)
                              (FFTW, the reference's DFT, is absent: float tolerance 2e-6 rms)
   srsran_chest_ul_estimate_pusch  the estimate rows, noise, CFO, TA, RSRP and EPRE against the oracle
-                             estimator fed the same DMRS (rtol 1e-4 on the estimate)
+                             estimator fed the same DMRS (within tests/pusch_cases.py: TOL, 4 x the distance of
+                             the compiled reference from a float64 evaluation; the oracle itself is held to the
+                             reference's fixtures in tests/test_pusch_golden.py)
   srsran_pusch_decode        CRC, payload, HARQ-ACK / RI / CQI and average iterations equal to the
                              oracle chain's, over QPSK / 16QAM / 64QAM, normal / extended CP, SRS
                              shortening, UCI, HARQ retransmission, a decoding failure and the
@@ -22,6 +24,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle"))
 sys.path.insert(0, HERE)
 
 import pusch as OP  # noqa: E402  (oracle/pusch.py)
+import pusch_cases as PC  # noqa: E402
 import pusch_tx as TX  # noqa: E402
 import uci_cases as UC  # noqa: E402
 
@@ -119,10 +122,15 @@ def _decode_case(po, case, rv=0, softbuffers=None, meas_ta=True, rng=None, grid_
     M = 12 * L
     rows = slice(n0 * 12, n0 * 12 + M)
     np.testing.assert_allclose(ce_gpu[:, rows], est["ce"][:, rows], rtol=1e-4, atol=1e-5)
-    assert ch.res.noise_estimate == pytest.approx(est["noise"], rel=2e-3, abs=1e-7)
-    assert ch.res.epre == pytest.approx(est["epre"], rel=1e-4)
-    assert ch.res.rsrp == pytest.approx(est["rsrp"], rel=1e-3, abs=1e-7)
-    assert ch.res.cfo_hz == pytest.approx(est["cfo_hz"], abs=0.5)
+    # kernel and oracle see the same DMRS here, so the tolerances derived from the reference's own float rounding
+    # (tests/pusch_cases.py: TOL) apply as they are
+    got = dict(ce=ce_gpu[:, rows], noise_estimate=ch.res.noise_estimate, epre=ch.res.epre, rsrp=ch.res.rsrp,
+               cfo_hz=ch.res.cfo_hz)
+    want = dict(ce=est["ce"][:, rows], noise_estimate=est["noise"], epre=est["epre"], rsrp=est["rsrp"], cfo_hz=est["cfo_hz"])
+    for k in got:
+        dist = PC.err(PC.KIND[k], got[k], want[k])
+        print(name, k, "%.3g (allowed %.3g)" % (dist, PC.TOL[k]))
+        assert dist <= PC.TOL[k], (k, dist)
     if meas_ta:
         assert abs(ch.res.ta_us - est["ta_us"]) <= 0.1 + 1e-6
     dsym = po.symbols(grid, est["ce"], est["noise"], cp, sh, L, cfg.grant.n_prb_tilde)

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle"))
 sys.path.insert(0, HERE)
 
 import pusch as OP  # noqa: E402  (oracle/pusch.py)
+import pusch_cases as PC  # noqa: E402
 import pusch_tx as TX  # noqa: E402
 import uci_cases as UC  # noqa: E402
 from srsran_4g_amd import pusch as P  # noqa: E402
@@ -66,6 +67,10 @@ def test_dmrs_matches_reference(po, cell_id):
             # u, v or alpha would differ by O(1) almost everywhere)
             err = np.abs(r - want)
             assert err.max() < 0.3 and np.mean(err > 1e-3) < 0.05 and np.median(err) < 1e-5
+            # and per configuration, against the exact float64 DMRS: 1.5 float ulp at its largest argument
+            exact, bound = PC.dmrs_exact(dict(cell_id=cell_id, cp=cp, L=n, tti=sf, n_dmrs=cs, dmrs=[
+                d.cyclic_shift, d.delta_ss, int(d.group_hopping_en), int(d.sequence_hopping_en)]))
+            assert PC.err("abs", r, exact) <= bound and PC.err("abs", want, exact) <= bound and err.max() <= 2 * bound
     d = P.srsran_refsignal_dmrs_pusch_cfg_t()
     d.cyclic_shift = 8
     assert P.dmrs(make_cell(nof_prb=25, cell_id=cell_id), d, 6, 0, 0)[0] != 0

@@ -6,6 +6,7 @@
  *   srsran_enb_dl_put_base (enb_dl.c:333-382): PSS / SSS in subframes 0 and 5 (pss.c:341-379,
  *     sss.c:105-119, gen_sss.c), the CRS (refsignal_cs_put_sf), the PBCH with the MIB of SFN tti / 10
  *     in subframe 0 (pbch.c srsran_pbch_mib_pack / srsran_pbch_encode), the PCFICH (pcfich.c:185-235),
+ *   srsran_enb_dl_put_phich (enb_dl.c:387-392 -> srsran_phich_calc + srsran_phich_encode, srsran_phich.h),
  *   srsran_enb_dl_put_pdcch_dl / _ul (enb_dl.c:392-428 -> srsran_pdcch_encode, pdcch.c:528-660) of
  *     messages packed with srsran_dci_msg_pack_pdsch / _pusch,
  *   srsran_enb_dl_put_pdsch (enb_dl.c:436-439 -> srsran_pdsch_encode, pdsch.c:1015-1120:
@@ -17,12 +18,12 @@
  * 0..3, 2 layers / 2 TBs or 1 TB with codebooks 0..2; codebook = pmi with one TB, pmi + 1 with two; one TB on two
  * layers carries 2 x the PDSCH REs modulation symbols, even ones on layer 0, odd ones on layer 1); normal or
  * extended CP;
- * rho_a = 1.  Not generated here (their REs stay empty): PHICH, MBSFN subframes.
+ * rho_a = 1.  Not generated here (their REs stay empty): MBSFN subframes.
  */
 #ifndef SRSRAN_AMD_ENB_DL_H
 #define SRSRAN_AMD_ENB_DL_H
 
-#include "srsran_pdcch.h"
+#include "srsran_phich.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -33,6 +34,12 @@ typedef struct {
   void*         gpu; /* added: encoder (srsran_sch_t), modulator (srsran_ofdm_t), grids, tables */
 } srsran_enb_dl_gpu_t;
 
+/* One HARQ indicator of a subframe. */
+typedef struct {
+  srsran_phich_resource_t n_phich;
+  uint8_t                 ack;
+} srsran_enb_dl_gpu_phich_t;
+
 /* Control channels of one subframe. */
 typedef struct {
   uint32_t                put_base; /* 1: PSS / SSS / PBCH / PCFICH as srsran_enb_dl_put_base adds them */
@@ -40,6 +47,9 @@ typedef struct {
   const srsran_dci_msg_t* dci;      /* host: packed DCI messages (payload, nof_bits, location, rnti), put in
                                        order as srsran_enb_dl_put_pdcch_dl / _ul would (a later message
                                        overwrites the CCEs it shares with an earlier one) */
+  uint32_t                         nof_phich; /* added: 0: no PHICH (nothing more is enqueued) */
+  const srsran_enb_dl_gpu_phich_t* phich;     /* host: HARQ indicators, summed per group in this order as consecutive
+                                                 srsran_phich_encode calls would; one launch for the whole batch */
 } srsran_enb_dl_gpu_ctrl_t;
 
 typedef struct {
@@ -76,8 +86,8 @@ void srsran_pbch_mib_pack(srsran_cell_t* cell, uint32_t sfn, uint8_t* payload);
 
 /* ---------------- enb/enb_dl.h (enb_dl.h:101-124): the reference's per-subframe eNB DL object ----------------
  * A srsENB caller's sequence per subframe, as lib/test/phy/phy_dl_test.c:152-196 and srsenb's cc_worker use it:
- *   srsran_enb_dl_put_base -> srsran_enb_dl_put_pdcch_dl / _ul (each DCI packed with srsran_dci_msg_pack_pdsch /
- *   _pusch at once, as enb_dl.c:392-428) -> srsran_enb_dl_put_pdsch -> srsran_enb_dl_gen_signal.
+ *   srsran_enb_dl_put_base -> srsran_enb_dl_put_phich (one per pending uplink ACK) -> srsran_enb_dl_put_pdcch_dl /
+ *   _ul (each DCI packed with srsran_dci_msg_pack_pdsch / _pusch at once, as enb_dl.c:392-428) -> srsran_enb_dl_put_pdsch -> srsran_enb_dl_gen_signal.
  * The puts record the subframe (the payloads copied to the device at once, so the caller may reuse its buffers);
  * srsran_enb_dl_gen_signal runs it through srsran_enb_dl_gpu_tx_batch (one subframe) and returns with the time
  * samples of every port in out_buffer[port] (host, SRSRAN_SF_LEN(symbol_sz) samples, the reference's amplitude
@@ -85,7 +95,7 @@ void srsran_pbch_mib_pack(srsran_cell_t* cell, uint32_t sfn, uint8_t* payload);
  * 10^(p_a / 20) x (sqrt 2 with more than one port) as srsran_pdsch_encode applies it (pdsch.c:492, 1066-1070).
  * Every subframe starts from srsran_enb_dl_put_base (the reference clears the grid there, enb_dl.c:376); a
  * subframe without it carries nothing of the previous one.  Not provided (their REs stay empty, an error message):
- * srsran_enb_dl_put_phich, srsran_enb_dl_put_pmch and MBSFN subframes. */
+ * srsran_enb_dl_put_pmch and MBSFN subframes. */
 typedef struct {
   srsran_cell_t         cell;
   srsran_dl_sf_cfg_t    dl_sf;
@@ -103,6 +113,10 @@ void srsran_enb_dl_free(srsran_enb_dl_t* q);                                    
 int  srsran_enb_dl_set_cell(srsran_enb_dl_t* q, srsran_cell_t cell);                                  /* enb_dl.c:142-235 */
 bool srsran_enb_dl_location_is_common_ncce(srsran_enb_dl_t* q, const srsran_dci_location_t* loc);    /* enb_dl.c:384-390 */
 void srsran_enb_dl_put_base(srsran_enb_dl_t* q, srsran_dl_sf_cfg_t* dl_sf);                           /* enb_dl.c:372-382 */
+/* Records one HARQ indicator for the subframe srsran_enb_dl_gen_signal sends; several a subframe, several in one
+ * group included, are all sent.  A grant whose resource is out of range is reported and dropped (the reference's
+ * srsran_phich_encode refuses it). */
+void srsran_enb_dl_put_phich(srsran_enb_dl_t* q, srsran_phich_grant_t* grant, bool ack);              /* enb_dl.c:387-392 */
 int  srsran_enb_dl_put_pdcch_dl(srsran_enb_dl_t* q, srsran_dci_cfg_t* dci_cfg, srsran_dci_dl_t* dci_dl); /* :392-408 */
 int  srsran_enb_dl_put_pdcch_ul(srsran_enb_dl_t* q, srsran_dci_cfg_t* dci_cfg, srsran_dci_ul_t* dci_ul); /* :410-428 */
 int  srsran_enb_dl_put_pdsch(srsran_enb_dl_t* q, srsran_pdsch_cfg_t* pdsch, uint8_t* data[SRSRAN_MAX_CODEWORDS]);

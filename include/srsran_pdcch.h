@@ -15,6 +15,7 @@
  * and one wave per PDCCH candidate for rate de-matching, quantisation, the 16-bit tail-biting
  * Viterbi decoder (64 lanes = 64 trellis states), CRC16 / RNTI and the re-encoding correlation.
  * Bit-exact with the reference's AVX2 build for the LLRs, decoded payloads and CRC remainders.
+ * The PHICH is in srsran_phich.h.
  * Provided: FDD, normal CP, 1, 2 or 4 ports, PHICH normal duration; DCI formats 0, 1, 1A, 1C
  * (size), 2, 2A; resource allocation types 0, 1 and 2 (localized).  Others return SRSRAN_ERROR.
  */
@@ -210,7 +211,11 @@ typedef struct {
   uint32_t              pdcch_nregs[3]; /* usable PDCCH REGs per CFI (multiple of 9) */
   uint32_t              pcfich_re[16];  /* added: grid indices l * 12 * nof_prb + k, srsran_regs_pcfich_get order */
   uint32_t*             pdcch_re[3];    /* added: 4 * pdcch_nregs[c] grid indices per CFI, srsran_regs_pdcch_get order */
+  uint32_t*             phich_re;       /* added: 12 grid indices per PHICH mapping unit, srsran_regs_phich_get order */
 } srsran_regs_t;
+/* ngroups_phich counts PHICH mapping units (phich_mi * ngroups_phich_m1) and srsran_regs_phich_ngroups returns
+ * it.  The reference doubles its ngroups_phich for the extended CP (regs.c:351-353: two groups share a unit);
+ * srsran_phich_ngroups (srsran_phich.h) returns that group count. */
 
 int      srsran_regs_init(srsran_regs_t* h, srsran_cell_t cell);                                       /* regs.c:706-709 */
 int      srsran_regs_init_opts(srsran_regs_t* h, srsran_cell_t cell, uint32_t phich_mi, bool mbsfn_or_sf1_6_tdd); /* regs.c:711-783 */

@@ -393,7 +393,7 @@ int srsran_pdsch_gpu_last_evm(srsran_pdsch_t* q, uint32_t sf, uint32_t tb, const
  * fft_mbsfn transforms antenna 0's input buffer into sf_symbols[0] and the other antennas' grids keep the
  * previous subframe, as in the reference (ue_dl.c:104-111, 353-356, 373-376); then the MBSFN estimator and the
  * PCFICH / PDCCH of the non-MBSFN region.  srsran_ue_dl_find_dl_dci / srsran_ue_dl_dci_to_pdsch_grant are in
- * srsran_pdcch.h.  PHICH / PMCH are not provided.  srsran_dl_cfg_t omits the reference's leading cqi_report, so
+ * srsran_pdcch.h, srsran_ue_dl_decode_phich in srsran_phich.h.  The PMCH is not provided.  srsran_dl_cfg_t omits the reference's leading cqi_report, so
  * srsran_ue_dl_gen_cqi_periodic / _aperiodic are not provided either; the feedback they report (RI, PMI, SINR) is:
  * section "channel-state feedback" at the end of this header. */
 typedef enum { SRSRAN_TM1 = 0, SRSRAN_TM2, SRSRAN_TM3, SRSRAN_TM4, SRSRAN_TM5, SRSRAN_TM6, SRSRAN_TM7, SRSRAN_TM8,

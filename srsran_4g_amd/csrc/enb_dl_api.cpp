@@ -1,7 +1,7 @@
 // srsran_4g_amd/csrc/enb_dl_api.cpp -- eNB downlink transmit on the GPU (include/srsran_enb_dl.h):
 // DL-SCH encoding (srsran_dlsch_gpu_encode_batch), CRS, scrambling + modulation + precoding + RE mapping
 // (llr_kernel.hip: pdsch_tx_kernel, crs_put_kernel), the control channels (ctrl_tx_kernel: PSS / SSS,
-// PBCH, PCFICH, PDCCH) and the OFDM modulator (ofdm_kernel.hip: ofdm_tx_kernel).  enb_dl.c:300-470,
+// PBCH, PCFICH, PDCCH; phich_kernel.hip: PHICH) and the OFDM modulator (ofdm_kernel.hip: ofdm_tx_kernel).  enb_dl.c:300-470,
 // pdsch.c:1015-1120, pdcch.c:528-660, pcfich.c:185-235, pbch.c, pss.c / sss.c / gen_sss.c.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -47,6 +47,8 @@ struct EnbDlGpu {
   float2*       d_sync  = nullptr;  // [PSS 72][SSS subframe 0: 72][SSS subframe 5: 72] (5 zero guards each side)
   CtrlTxJob*    d_jobs  = nullptr;
   size_t        jobs_cap = 0;
+  srsran_phich_t phich{};  // PHICH transmitter on `regs` (created with the first subframe that carries one)
+  bool           phich_ok = false;
 };
 
 constexpr size_t kTabCache = 512;  // RE tables kept on the device
@@ -330,6 +332,9 @@ void srsran_enb_dl_gpu_free(srsran_enb_dl_gpu_t* q)
     hipFree(g->d_ctab);
     hipFree(g->d_sync);
     hipFree(g->d_jobs);
+    if (g->phich_ok) {
+      srsran_phich_free(&g->phich);
+    }
     if (g->regs_ok) {
       srsran_regs_free(&g->regs);
     }
@@ -482,6 +487,36 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
   if (!grow((void**)&g->d_jobs, &g->jobs_cap, std::max<size_t>(jobs.size(), 1) * sizeof(CtrlTxJob))) {
     return SRSRAN_ERROR;
   }
+  // HARQ indicators of every subframe: one launch after the grid clear (their REs are no other channel's)
+  std::vector<srsran_phich_gpu_item_t> hi;
+  for (uint32_t b = 0; b < nof_sf; b++) {
+    const srsran_enb_dl_gpu_ctrl_t* c = sfs[b].ctrl;
+    if (!c || c->nof_phich == 0) {
+      continue;
+    }
+    if (!c->phich) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    for (uint32_t i = 0; i < c->nof_phich; i++) {
+      const bool ext = cell.cp == SRSRAN_CP_EXT;  // srsran_phich_encode's checks, before anything is enqueued
+      if (c->phich[i].n_phich.nseq >= (ext ? SRSRAN_PHICH_EXT_NSEQUENCES : SRSRAN_PHICH_NORM_NSEQUENCES) ||
+          c->phich[i].n_phich.ngroup >= g->regs.ngroups_phich * (ext ? 2u : 1u)) {
+        fprintf(stderr, "[srsran_enb_dl] invalid PHICH resource ngroup %u, nseq %u\n", c->phich[i].n_phich.ngroup,
+                c->phich[i].n_phich.nseq);
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
+      hi.push_back({b, sfs[b].tti, c->phich[i].n_phich, c->phich[i].ack});
+    }
+  }
+  if (!hi.empty() && !g->phich_ok) {
+    if (srsran_phich_init(&g->phich, 1) != SRSRAN_SUCCESS) {
+      return SRSRAN_ERROR;
+    }
+    g->phich_ok = true;
+    if (srsran_phich_set_cell(&g->phich, &g->regs, cell) != SRSRAN_SUCCESS) {
+      return SRSRAN_ERROR;
+    }
+  }
   if ((!enc.empty() && srsran_dlsch_gpu_encode_batch(&g->sch, (uint32_t)enc.size(), enc.data(), st) != SRSRAN_SUCCESS) ||
       hipMemsetAsync(g->d_grid, 0, grid_bytes, st) != hipSuccess ||
       (npd && hipMemcpyAsync(g->d_items, items.data(), npd * sizeof(PdschTx), hipMemcpyHostToDevice, st) != hipSuccess) ||
@@ -492,6 +527,11 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
       ctrl_tx_launch(g->d_jobs, (uint32_t)jobs.size(), st) != hipSuccess ||
       pdsch_tx_launch(g->d_items, npd, max_nre, st) != hipSuccess) {
     return SRSRAN_ERROR;
+  }
+  if (!hi.empty()) {
+    if (int r = srsran_phich_gpu_encode_batch(&g->phich, (uint32_t)hi.size(), hi.data(), nof_sf, (cf_t*)g->d_grid, st)) {
+      return r;
+    }
   }
   g->last_sf = nof_sf;
   const float sc = scale > 0.0f ? scale : 0.05f / sqrtf((float)cell.nof_prb);  // enb_dl_get_norm_factor
@@ -509,6 +549,7 @@ struct EnbDlRef {
   // the subframe being recorded (srsran_enb_dl_put_* until srsran_enb_dl_gen_signal)
   bool                          base = false, pdsch = false;
   std::vector<srsran_dci_msg_t> dci;
+  std::vector<srsran_enb_dl_gpu_phich_t> phich;
   srsran_pdsch_cfg_t            cfg{};
   uint8_t*                      d_data[SRSRAN_MAX_CODEWORDS] = {nullptr, nullptr};
   size_t                        data_cap = 0;
@@ -639,6 +680,31 @@ void srsran_enb_dl_put_base(srsran_enb_dl_t* q, srsran_dl_sf_cfg_t* dl_sf)
   g->base     = true;  // clear_sf + sync + CRS + MIB + PCFICH (enb_dl.c:372-382), generated with the subframe
   g->pdsch    = false;
   g->dci.clear();
+  g->phich.clear();
+}
+
+void srsran_enb_dl_put_phich(srsran_enb_dl_t* q, srsran_phich_grant_t* grant, bool ack)
+{
+  if (!q || !q->gpu || !grant || !q->cell.nof_prb) {
+    return;
+  }
+  EnbDlRef* g = (EnbDlRef*)q->gpu;
+  // srsran_phich_calc on the cell's tables (m_i = 1), then srsran_phich_encode's checks (phich.c:326-340)
+  const bool     ext = q->cell.cp == SRSRAN_CP_EXT;
+  const uint32_t m1 = q->regs.ngroups_phich_m1, nsf = ext ? SRSRAN_PHICH_EXT_NSF : SRSRAN_PHICH_NORM_NSF;
+  if (m1 == 0) {
+    fprintf(stderr, "[srsran_enb_dl] Error computing PHICH groups. Ngroups is zero\n");
+    return;
+  }
+  srsran_enb_dl_gpu_phich_t h;
+  h.n_phich.ngroup = (grant->n_prb_lowest + grant->n_dmrs) % m1 + grant->I_phich * m1;
+  h.n_phich.nseq   = ((grant->n_prb_lowest / m1) + grant->n_dmrs) % (2 * nsf);
+  h.ack            = ack ? 1 : 0;
+  if (h.n_phich.ngroup >= q->regs.ngroups_phich * (ext ? 2u : 1u)) {
+    fprintf(stderr, "[srsran_enb_dl] Invalid PHICH ngroup %u\n", h.n_phich.ngroup);
+    return;
+  }
+  g->phich.push_back(h);
 }
 
 static int put_dci(srsran_enb_dl_t* q, const srsran_dci_msg_t& m)
@@ -754,6 +820,8 @@ void srsran_enb_dl_gen_signal(srsran_enb_dl_t* q)
   ctrl.put_base = g->base ? 1u : 0u;
   ctrl.nof_dci  = (uint32_t)g->dci.size();
   ctrl.dci      = g->dci.empty() ? nullptr : g->dci.data();
+  ctrl.nof_phich = (uint32_t)g->phich.size();
+  ctrl.phich     = g->phich.empty() ? nullptr : g->phich.data();
   srsran_enb_dl_gpu_sf_t sf;
   memset(&sf, 0, sizeof(sf));
   sf.tti  = q->dl_sf.tti;
@@ -781,6 +849,7 @@ void srsran_enb_dl_gen_signal(srsran_enb_dl_t* q)
   g->base  = false;
   g->pdsch = false;
   g->dci.clear();
+  g->phich.clear();
 }
 
 float srsran_enb_dl_get_maximum_signal_power_dBfs(uint32_t nof_prb)

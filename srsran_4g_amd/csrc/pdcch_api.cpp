@@ -151,6 +151,11 @@ int build_regs(srsran_regs_t* h, uint32_t phich_mi, bool mbsfn_or_sf1_6)
   }
   h->ngroups_phich_m1 = (uint32_t)(int)ceilf(ng * ((float)nprb / 8));
   h->ngroups_phich    = phich_mi * h->ngroups_phich_m1;
+  // the mapping units' REs, kept for the PHICH itself (srsran_regs_phich_get / _add order, regs.c:421-481)
+  h->phich_re = (uint32_t*)malloc(12 * (size_t)std::max(1u, h->ngroups_phich) * sizeof(uint32_t));
+  if (!h->phich_re) {
+    return SRSRAN_ERROR;
+  }
   if (h->ngroups_phich) {
     const bool        ext = h->phich_len == SRSRAN_PHICH_EXT;
     std::vector<Reg*> lr[3];  // free REGs of symbols 0-2, lowest frequency first
@@ -171,6 +176,9 @@ int build_regs(srsran_regs_t* h, uint32_t phich_mi, bool mbsfn_or_sf1_6)
         }
         const uint32_t ni = ((c.id * n[li] / (ext && mbsfn_or_sf1_6 ? n[1] : n[0])) + mi + q * n[li] / 3) % n[li];
         lr[li][ni]->assigned = true;
+        for (int e = 0; e < 4; e++) {
+          h->phich_re[12 * mi + 4 * q + e] = lr[li][ni]->k[e] + lr[li][ni]->l * nre;
+        }
       }
     }
   }
@@ -400,6 +408,7 @@ void srsran_regs_free(srsran_regs_t* h)
   for (int c = 0; c < 3; c++) {
     free(h->pdcch_re[c]);
   }
+  free(h->phich_re);
   memset(h, 0, sizeof(*h));
 }
 

@@ -17,7 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/srsran_pdcch.h"
+#include "../../include/srsran_phich.h"
 #include "chest_kernel.h"
 #include "csi_kernel.h"
 #include "pdsch_internal.h"
@@ -52,6 +52,7 @@ struct UeDlGpu {
   srsran_regs_t         regs{};
   srsran_pcfich_t       pcfich{};
   srsran_pdcch_t        pdcch{};
+  srsran_phich_t        phich{};
   bool                  ctrl_init = false;  // objects allocated (<= 2 rx antennas)
   bool                  ctrl_cell = false;  // tables built for the current cell
   srsran_dci_location_t allocated[SRSRAN_MAX_DCI_MSG];
@@ -75,9 +76,9 @@ const uint8_t kMiTdd[7][10] = {{2, 1, 0, 0, 0, 2, 1, 0, 0, 0}, {0, 1, 0, 0, 1, 0
                                {0, 0, 0, 0, 0, 0, 0, 0, 1, 1}, {0, 0, 0, 0, 0, 0, 0, 0, 1, 0},
                                {1, 1, 0, 0, 0, 1, 1, 0, 0, 1}};
 
-// set_mi_value (ue_dl.c:296-313): the PDCCH works on the REG tables of the selected m_i (MI_VALUE: 1 for FDD, the
-// table above for TDD)
-void select_mi(UeDlGpu* g, const srsran_cell_t& cell, const srsran_dl_sf_cfg_t* sf)
+// set_mi_value (ue_dl.c:296-313): the PDCCH and the PHICH work on the REG tables of the selected m_i (MI_VALUE: 1 for
+// FDD, the table above for TDD)
+srsran_regs_t* mi_table(UeDlGpu* g, const srsran_cell_t& cell, const srsran_dl_sf_cfg_t* sf)
 {
   const uint32_t auto_mi = cell.frame_type == SRSRAN_FDD || sf->tdd_config.sf_config >= 7
                                ? 1u
@@ -87,7 +88,12 @@ void select_mi(UeDlGpu* g, const srsran_cell_t& cell, const srsran_dl_sf_cfg_t* 
   // manual choice never adds it (ue_dl.c:308-311)
   const bool           ext = g->mi_auto && g->ext_tables && (sf->tti % 10 == 1 || sf->tti % 10 == 6);
   const uint32_t       i   = mi == 1 ? 0 : mi == 0 ? 1 : 2;  // mi_reg_idx_inv
-  srsran_regs_t* const t   = ext ? &g->regs_ext[i] : i == 0 ? &g->regs : &g->regs_mi[i - 1];
+  return ext ? &g->regs_ext[i] : i == 0 ? &g->regs : &g->regs_mi[i - 1];
+}
+
+void select_mi(UeDlGpu* g, const srsran_cell_t& cell, const srsran_dl_sf_cfg_t* sf)
+{
+  srsran_regs_t* const t = mi_table(g, cell, sf);
   if (t != g->regs_set) {
     srsran_pdcch_set_regs(&g->pdcch, t);
     g->regs_set = t;
@@ -182,7 +188,8 @@ int srsran_ue_dl_init(srsran_ue_dl_t* q, cf_t* input[SRSRAN_MAX_PORTS], uint32_t
     }
   }
   if (nof_rx_antennas <= 2) {
-    if (srsran_pcfich_init(&g->pcfich, nof_rx_antennas) || srsran_pdcch_init_ue(&g->pdcch, max_prb, nof_rx_antennas)) {
+    if (srsran_pcfich_init(&g->pcfich, nof_rx_antennas) || srsran_pdcch_init_ue(&g->pdcch, max_prb, nof_rx_antennas) ||
+        srsran_phich_init(&g->phich, nof_rx_antennas)) {
       srsran_ue_dl_free(q);
       return SRSRAN_ERROR;
     }
@@ -211,6 +218,9 @@ void srsran_ue_dl_free(srsran_ue_dl_t* q)
     if (g->ctrl_init) {
       srsran_pcfich_free(&g->pcfich);
       srsran_pdcch_free(&g->pdcch);
+    }
+    if (g->phich.gpu) {
+      srsran_phich_free(&g->phich);
     }
     srsran_regs_free(&g->regs);
     srsran_regs_free(&g->regs_mi[0]);
@@ -281,7 +291,8 @@ int srsran_ue_dl_set_cell(srsran_ue_dl_t* q, srsran_cell_t cell)
                                      srsran_regs_init_opts(&g->regs_ext[1], cell, 0, true) == SRSRAN_SUCCESS &&
                                      srsran_regs_init_opts(&g->regs_ext[2], cell, 2, true) == SRSRAN_SUCCESS)) &&
                  srsran_pcfich_set_cell(&g->pcfich, &g->regs, cell) == SRSRAN_SUCCESS &&
-                 srsran_pdcch_set_cell(&g->pdcch, &g->regs, cell) == SRSRAN_SUCCESS;
+                 srsran_pdcch_set_cell(&g->pdcch, &g->regs, cell) == SRSRAN_SUCCESS &&
+                 srsran_phich_set_cell(&g->phich, &g->regs, cell) == SRSRAN_SUCCESS;
   g->regs_set = &g->regs;
   g->nof_pending_ul = 0;  // ue_dl.c:189
   hipDeviceSynchronize();
@@ -357,6 +368,31 @@ int srsran_ue_dl_decode_fft_estimate_noguru(srsran_ue_dl_t*     q,
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   return fft_estimate(q, sf, cfg, input);
+}
+
+int srsran_ue_dl_decode_phich(srsran_ue_dl_t* q, srsran_dl_sf_cfg_t* sf, srsran_ue_dl_cfg_t* cfg,
+                              srsran_phich_grant_t* grant, srsran_phich_res_t* result)
+{
+  if (!q || !q->gpu || !sf || !grant) {
+    return -1;
+  }
+  UeDlGpu* g = (UeDlGpu*)q->gpu;
+  if (!g->ctrl_cell || !g->have_est) {
+    fprintf(stderr, "[srsran_ue_dl] PHICH: no control-channel tables or no estimate for this cell\n");
+    return -1;
+  }
+  (void)cfg;
+  srsran_regs_t* const t = mi_table(g, q->cell, sf);  // set_mi_value
+  if (t != g->phich.regs) {
+    srsran_phich_set_regs(&g->phich, t);
+  }
+  srsran_phich_resource_t n_phich = {0, 0};
+  srsran_phich_calc(&g->phich, grant, &n_phich);
+  if (srsran_phich_decode(&g->phich, sf, &q->chest_res, n_phich, q->sf_symbols, result) != SRSRAN_SUCCESS) {
+    fprintf(stderr, "[srsran_ue_dl] Error decoding PHICH\n");
+    return -1;
+  }
+  return 0;
 }
 
 int srsran_ue_dl_decode_pdsch(srsran_ue_dl_t*     q,

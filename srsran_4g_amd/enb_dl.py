@@ -1,9 +1,11 @@
 """Python mirror of include/srsran_enb_dl.h: downlink subframes transmitted on the GPU (DL-SCH encode,
-CRS, scrambling / modulation / precoding / RE mapping, PSS / SSS / PBCH / PCFICH / PDCCH, OFDM
+CRS, scrambling / modulation / precoding / RE mapping, PSS / SSS / PBCH / PCFICH / PHICH / PDCCH, OFDM
 modulator).  No CPU fallback."""
 import ctypes
 
-from .pdcch import srsran_dci_dl_t, srsran_dci_location_t, srsran_dci_msg_t, srsran_pdcch_t, srsran_regs_t
+from .pdcch import (srsran_dci_dl_t, srsran_dci_location_t, srsran_dci_msg_t, srsran_dci_ul_t, srsran_pdcch_t,
+                    srsran_regs_t)
+from .phich import srsran_phich_grant_t, srsran_phich_resource_t
 from .sch import srsran_pdsch_cfg_t
 from .tdec import load_library
 from .ue_dl import srsran_cell_t, srsran_dci_cfg_t, srsran_dl_sf_cfg_t
@@ -15,8 +17,13 @@ class srsran_enb_dl_gpu_t(ctypes.Structure):
     _fields_ = [("cell", srsran_cell_t), ("gpu", ctypes.c_void_p)]
 
 
+class srsran_enb_dl_gpu_phich_t(ctypes.Structure):
+    _fields_ = [("n_phich", srsran_phich_resource_t), ("ack", ctypes.c_uint8)]
+
+
 class srsran_enb_dl_gpu_ctrl_t(ctypes.Structure):
-    _fields_ = [("put_base", u32), ("nof_dci", u32), ("dci", ctypes.POINTER(srsran_dci_msg_t))]
+    _fields_ = [("put_base", u32), ("nof_dci", u32), ("dci", ctypes.POINTER(srsran_dci_msg_t)),
+                ("nof_phich", u32), ("phich", ctypes.POINTER(srsran_enb_dl_gpu_phich_t))]
 
 
 class srsran_enb_dl_gpu_sf_t(ctypes.Structure):
@@ -55,6 +62,9 @@ def lib():
                 ("srsran_enb_dl_put_base", [R, ctypes.POINTER(srsran_dl_sf_cfg_t)], None),
                 ("srsran_enb_dl_put_pdcch_dl", [R, ctypes.POINTER(srsran_dci_cfg_t), ctypes.POINTER(srsran_dci_dl_t)],
                  ctypes.c_int),
+                ("srsran_enb_dl_put_pdcch_ul", [R, ctypes.POINTER(srsran_dci_cfg_t), ctypes.POINTER(srsran_dci_ul_t)],
+                 ctypes.c_int),
+                ("srsran_enb_dl_put_phich", [R, ctypes.POINTER(srsran_phich_grant_t), ctypes.c_bool], None),
                 ("srsran_enb_dl_put_pdsch", [R, ctypes.POINTER(srsran_pdsch_cfg_t), ctypes.c_void_p * 2], ctypes.c_int),
                 ("srsran_enb_dl_gen_signal", [R], None),
                 ("srsran_enb_dl_get_maximum_signal_power_dBfs", [u32], ctypes.c_float)):
@@ -72,7 +82,8 @@ class EnbDl:
 
     def tx_batch(self, sfs, d_samples, scale=0.0, stream=None, pdsch_scaling=0.0):
         """sfs: list of (tti, cfi, srsran_pdsch_cfg_t or None, [device payload pointers][, ctrl]) with ctrl =
-        (put_base, [srsran_dci_msg_t, ...]) or None; pdsch_scaling: every subframe's precoder scaling (<= 0: 1).
+        (put_base, [srsran_dci_msg_t, ...][, [(ngroup, nseq, ack), ...]]) or None (the third member: the subframe's
+        HARQ indicators); pdsch_scaling: every subframe's precoder scaling (<= 0: 1).
         The transmission scheme is the grant's: cfg.grant.tx_scheme with nof_layers, nof_tb and pmi (ue_dl.pdsch_cfg
         scheme="port0" / "diversity" / "cdd" / "sm", pmi=, layers= for one codeword on two layers)"""
         arr = (srsran_enb_dl_gpu_sf_t * len(sfs))()
@@ -88,11 +99,18 @@ class EnbDl:
             for j, p in enumerate(ptrs):
                 arr[i].d_data[j] = p
             if ctrl is not None:
-                put_base, msgs = ctrl
+                put_base, msgs = ctrl[:2]
+                his = ctrl[2] if len(ctrl) > 2 else []
                 c = srsran_enb_dl_gpu_ctrl_t()
                 c.put_base = 1 if put_base else 0
                 m = (srsran_dci_msg_t * max(1, len(msgs)))(*msgs)
                 c.nof_dci, c.dci = len(msgs), ctypes.cast(m, ctypes.POINTER(srsran_dci_msg_t))
+                if his:
+                    h = (srsran_enb_dl_gpu_phich_t * len(his))()
+                    for k, (ngroup, nseq, ack) in enumerate(his):
+                        h[k].n_phich.ngroup, h[k].n_phich.nseq, h[k].ack = ngroup, nseq, ack
+                    c.nof_phich, c.phich = len(his), ctypes.cast(h, ctypes.POINTER(srsran_enb_dl_gpu_phich_t))
+                    self._keep.append(h)
                 arr[i].ctrl = ctypes.pointer(c)
                 self._keep += [c, m]
         return lib().srsran_enb_dl_gpu_tx_batch(ctypes.byref(self.q), len(sfs), arr, d_samples, scale, stream)
@@ -132,6 +150,14 @@ class EnbDlRef:
 
     def put_pdcch_dl(self, dci_cfg, dci):
         return lib().srsran_enb_dl_put_pdcch_dl(ctypes.byref(self.q), ctypes.byref(dci_cfg), ctypes.byref(dci))
+
+    def put_pdcch_ul(self, dci_cfg, dci):
+        return lib().srsran_enb_dl_put_pdcch_ul(ctypes.byref(self.q), ctypes.byref(dci_cfg), ctypes.byref(dci))
+
+    def put_phich(self, n_prb_lowest, n_dmrs, ack, I_phich=0):
+        g = srsran_phich_grant_t()
+        g.n_prb_lowest, g.n_dmrs, g.I_phich = n_prb_lowest, n_dmrs, I_phich
+        lib().srsran_enb_dl_put_phich(ctypes.byref(self.q), ctypes.byref(g), bool(ack))
 
     def put_pdsch(self, cfg, payloads):
         self._pl = [self.np.ascontiguousarray(p) for p in payloads]

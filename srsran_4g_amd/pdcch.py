@@ -18,7 +18,8 @@ FORMAT0, FORMAT1, FORMAT1A, FORMAT1B, FORMAT1C, FORMAT1D, FORMAT2, FORMAT2A, FOR
 class srsran_regs_t(ctypes.Structure):
     _fields_ = [("cell", srsran_cell_t), ("max_ctrl_symbols", u32), ("ngroups_phich", u32), ("ngroups_phich_m1", u32),
                 ("phich_res", ctypes.c_int), ("phich_len", ctypes.c_int), ("phich_mi", u32),
-                ("pdcch_nregs", u32 * 3), ("pcfich_re", u32 * 16), ("pdcch_re", ctypes.POINTER(u32) * 3)]
+                ("pdcch_nregs", u32 * 3), ("pcfich_re", u32 * 16), ("pdcch_re", ctypes.POINTER(u32) * 3),
+                ("phich_re", ctypes.POINTER(u32))]
 
 
 class srsran_pcfich_t(ctypes.Structure):
@@ -190,6 +191,13 @@ class Regs:
     def pdcch_re(self, cfi):
         n = 4 * self.q.pdcch_nregs[cfi - 1]
         return np.ctypeslib.as_array(self.q.pdcch_re[cfi - 1], (n,)).copy()
+
+    def phich_re(self):
+        """(mapping units, 12) grid indices, srsran_regs_phich_get order"""
+        n = self.q.ngroups_phich
+        if n == 0:
+            return np.zeros((0, 12), np.uint32)
+        return np.ctypeslib.as_array(self.q.phich_re, (n, 12)).copy()
 
     def free(self):
         lib().srsran_regs_free(ctypes.byref(self.q))

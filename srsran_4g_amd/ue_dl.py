@@ -690,6 +690,11 @@ class UeDl:
             raise RuntimeError("srsran_ue_dl_find_ul_dci failed")
         return [out[i] for i in range(n)]
 
+    def decode_phich(self, tti, cfi, n_prb_lowest, n_dmrs, I_phich=0):
+        """srsran_ue_dl_decode_phich (after fft_estimate) -> (ret, ack_value, distance)"""
+        from . import phich as PH
+        return PH.ue_decode_phich(self.q, sf_cfg(tti, cfi, self.tdd), self.cfg, n_prb_lowest, n_dmrs, I_phich)
+
     def set_mi(self, mi_idx=None):
         """srsran_ue_dl_set_mi_auto (None) / srsran_ue_dl_set_mi_manual(mi_idx)"""
         if mi_idx is None:

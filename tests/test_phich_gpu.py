@@ -1,0 +1,338 @@
+"""PHICH on the GPU against the fixture recorded from the compiled reference (tests/golden/make_phich_golden.py,
+cases in tests/phich_cases.py).
+
+Transmit: srsran_phich_encode, srsran_phich_gpu_encode_batch and srsran_enb_dl_gpu_tx_batch with nof_phich > 0 equal
+the reference's grids on every RE within 1e-6 x max(1, max |grid|) (the control-channel bound of
+tests/test_enb_ctrl_gpu.py); REs outside the PHICH units equal the batch without PHICH bit for bit; a batch of
+several subframes equals the single-subframe calls bit for bit.
+Receive: srsran_phich_decode and srsran_phich_gpu_decode_batch on the fixture's grids and estimates give the
+reference's ack_value wherever something was sent and its distance within max(4 x the fixture's reference-to-float64
+distance of the case, 1e-6 x max(1, |distance|)); batch results are bit-identical to one-item calls; out-of-range
+resources return the reference's error.
+Loop: srsran_enb_dl_put_base / put_phich / put_pdcch_ul / gen_signal -> srsran_ue_dl_decode_fft_estimate ->
+srsran_ue_dl_decode_phich returns every indicator as sent, the UL DCI is still found, and the result equals
+srsran_phich_decode on the UE object's own grids and estimates exactly."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = np.load(os.path.join(ROOT, "tests", "golden", "phich_golden.npz"))
+META = json.loads(bytes(GOLD["meta"]).decode())
+CASES = META["cases"]
+ROWS = META["rows"]
+SENT = [c for c in CASES if c["items"]]
+ENB = [c for c in SENT if c["mi"] == 1 and not c["sf1_6"]]  # the eNB transmitter's tables: m_i = 1
+ids = lambda cs: [c["name"] for c in cs]  # noqa: E731
+
+
+@pytest.fixture(scope="module")
+def mods():
+    from srsran_4g_amd import tdec
+    if not tdec.gpu_available():
+        pytest.fail("no HIP device on a GPU test run")
+    import torch
+    from srsran_4g_amd import enb_dl as E
+    from srsran_4g_amd import pdcch as PD
+    from srsran_4g_amd import phich as PH
+    from srsran_4g_amd import ue_dl as U
+    U.use_standard_symbol_size(True)
+    return torch, PD, PH, E, U
+
+
+def make_cell(PD, c):
+    cl = PD.cell(c["nof_prb"], c["ports"], c["cell_id"], c["phich_len"], c["phich_res"], c["cp"])
+    cl.frame_type = c["frame"]
+    return cl
+
+
+def sf_re(c):
+    return 2 * (6 if c["cp"] else 7) * 12 * c["nof_prb"]
+
+
+def full(c, planes):
+    """(..., ROWS * nre) of the fixture -> (..., sf_re) with the other symbols zero"""
+    out = np.zeros(planes.shape[:-1] + (sf_re(c),), np.complex64)
+    out[..., :planes.shape[-1]] = planes
+    return out
+
+
+def to_dev(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.complex64).view(np.float32)).cuda()
+
+
+def to_host(t, shape):
+    return t.cpu().numpy().view(np.complex64).reshape(shape)
+
+
+def bits(a):
+    """the array's 32-bit words, for bit-for-bit comparisons"""
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def tx_bound(want):
+    return 1e-6 * max(1.0, float(np.abs(want).max()))
+
+
+class Obj:
+    def __init__(self, mods, c):
+        _, PD, PH, _, _ = mods
+        self.cell = make_cell(PD, c)
+        self.regs = PD.Regs(self.cell, c["mi"], c["sf1_6"])
+        self.ph = PH.Phich(self.cell, self.regs, c["nrx"])
+
+    def free(self):
+        self.ph.free()
+        self.regs.free()
+
+
+# ------------------------------------------------------------------ transmit
+@pytest.mark.parametrize("c", SENT, ids=ids(SENT))
+def test_encode_host_and_batch_equal_reference(mods, c):
+    torch = mods[0]
+    want = full(c, GOLD[c["name"] + "/tx"])
+    o = Obj(mods, c)
+    try:
+        assert o.ph.ngroups() == c["ngroups"]
+        host = [np.zeros(sf_re(c), np.complex64) for _ in range(c["ports"])]
+        for g, s, a in c["items"]:
+            assert o.ph.encode(c["tti"], g, s, a, host) == 0
+        err = float(np.abs(np.stack(host) - want).max())
+        d = torch.zeros((1, c["ports"], sf_re(c), 2), dtype=torch.float32, device="cuda")
+        assert o.ph.encode_batch([(0, c["tti"], g, s, a) for g, s, a in c["items"]], 1, d.data_ptr()) == 0
+        torch.cuda.synchronize()
+        got = to_host(d, (c["ports"], sf_re(c)))
+        errb = float(np.abs(got - want).max())
+        print(f"{c['name']}: transmit max |GPU - reference| host {err:.3e} batch {errb:.3e} bound {tx_bound(want):.3e}")
+        assert err <= tx_bound(want) and errb <= tx_bound(want)
+        assert np.count_nonzero(want) > 0
+    finally:
+        o.free()
+
+
+INVALID = [c for c in CASES if c["invalid_ret"]]
+
+
+@pytest.mark.parametrize("c", INVALID, ids=ids(INVALID))
+def test_invalid_resources_return_the_references_error(mods, c):
+    torch, _, PH, _, _ = mods
+    o = Obj(mods, c)
+    try:
+        zero_g = np.zeros((c["nrx"], sf_re(c)), np.complex64)
+        zero_h = np.zeros((c["ports"], c["nrx"], sf_re(c)), np.complex64)
+        for g, s, enc_ret, dec_ret in c["invalid_ret"]:
+            assert enc_ret == dec_ret == PH.ERROR_INVALID_INPUTS  # what the reference answered
+            host = [np.zeros(sf_re(c), np.complex64) for _ in range(c["ports"])]
+            assert o.ph.encode(c["tti"], g, s, 1, host) == enc_ret
+            assert not np.stack(host).any()
+            assert o.ph.decode(c["tti"], g, s, zero_g, zero_h, 0.0)[0] == dec_ret
+            d = torch.zeros((1, c["ports"], sf_re(c), 2), dtype=torch.float32, device="cuda")
+            res = torch.zeros((2, 2), dtype=torch.float32, device="cuda")
+            items = ([(0, c["tti"], c["items"][0][0], c["items"][0][1], 1)] if c["items"] else []) + \
+                [(0, c["tti"], g, s, 1)]
+            assert o.ph.encode_batch(items, 1, d.data_ptr()) == enc_ret
+            assert o.ph.decode_batch(items, 1, d.data_ptr(), d.data_ptr(), sf_re(c), res.data_ptr(), 0,
+                                     res.data_ptr()) == dec_ret
+            torch.cuda.synchronize()
+            assert not d.cpu().numpy().any()  # nothing was enqueued, not even the valid item
+    finally:
+        o.free()
+
+
+MULTI = [c for c in SENT if c["name"] in ("p25_ng1_2p", "extcp_1p", "p15_4p")]
+
+
+@pytest.mark.parametrize("c", MULTI, ids=ids(MULTI))
+def test_encode_batch_of_subframes_equals_single_calls(mods, c):
+    torch = mods[0]
+    o = Obj(mods, c)
+    try:
+        its = c["items"]
+        per_sf = [(c["tti"], its), (c["tti"] + 3, its[::-1]), (c["tti"] + 15, its[:2])]
+        batch = [(b, tti, g, s, a) for b, (tti, sub) in enumerate(per_sf) for g, s, a in sub]
+        batch = batch[1::2] + batch[0::2]  # subframes interleaved: only the order inside a group matters
+        d = torch.zeros((3, c["ports"], sf_re(c), 2), dtype=torch.float32, device="cuda")
+        assert o.ph.encode_batch(batch, 3, d.data_ptr()) == 0
+        torch.cuda.synchronize()
+        got = to_host(d, (3, c["ports"], sf_re(c)))
+        for b, (tti, sub) in enumerate(per_sf):
+            d1 = torch.zeros((1, c["ports"], sf_re(c), 2), dtype=torch.float32, device="cuda")
+            single = [x for x in batch if x[0] == b]
+            assert o.ph.encode_batch([(0,) + x[1:] for x in single], 1, d1.data_ptr()) == 0
+            torch.cuda.synchronize()
+            want = to_host(d1, (c["ports"], sf_re(c)))
+            assert np.array_equal(bits(got[b]), bits(want)), b
+            assert np.count_nonzero(want) > 0
+        assert not np.array_equal(got[0], got[1])  # another subframe, another scrambling sequence
+    finally:
+        o.free()
+
+
+@pytest.mark.parametrize("c", ENB, ids=ids(ENB))
+def test_enb_tx_batch_with_phich(mods, c):
+    torch, PD, _, E, U = mods
+    cell = make_cell(PD, c)
+    P, n = c["ports"], sf_re(c)
+    N = U.lib().srsran_symbol_sz(c["nof_prb"])
+    enb = E.EnbDl(cell)
+    try:
+        d_out = torch.zeros((2, P, 15 * N, 2), dtype=torch.float32, device="cuda")
+        m = PD.srsran_dci_msg_t()
+        m.payload[:30] = [1, 0] * 15
+        m.nof_bits, m.rnti = 30, 0x46
+        m.location.L, m.location.ncce = 0, 0
+
+        def run(with_phich):
+            his = [tuple(i) for i in c["items"]] if with_phich else []
+            sfs = [(c["tti"], 3, None, [], (True, [m], his)), (c["tti"] + 1, 3, None, [], (True, [], []))]
+            assert enb.tx_batch(sfs, d_out.data_ptr(), 1.0) == 0
+            torch.cuda.synchronize()
+            from srsran_4g_amd.sch import _memcpy_d2h
+            host = torch.empty(2 * 2 * P * n, dtype=torch.float32)
+            _memcpy_d2h(host, enb.sf_symbols(), 2 * P * n * 8)
+            return host.numpy().view(np.complex64).reshape(2, P, n).copy(), to_host(d_out, (2, P, 15 * N)).copy()
+
+        plain, plain_t = run(False)
+        got, got_t = run(True)
+        re = GOLD[c["name"] + "/re"].ravel()
+        want = full(c, GOLD[c["name"] + "/tx"])
+        err = float(np.abs(got[0][:, re] - want[:, re]).max())
+        print(f"{c['name']}: eNB batch PHICH REs max |GPU - reference| {err:.3e} bound {tx_bound(want):.3e}")
+        assert err <= tx_bound(want)
+        assert not plain[0][:, re].any()  # empty without PHICH
+        mask = np.ones(n, bool)
+        mask[re] = False
+        assert np.array_equal(bits(got[0][:, mask]), bits(plain[0][:, mask]))
+        assert np.array_equal(bits(got[1]), bits(plain[1]))  # the subframe without PHICH
+        assert np.array_equal(bits(got_t[1]), bits(plain_t[1]))
+        assert not np.array_equal(got_t[0], plain_t[0])  # the indicators reach the time samples
+        # an out-of-range indicator refuses the batch
+        bad = [(c["tti"], 3, None, [], (True, [], [(c["ngroups"], 0, 1)]))]
+        assert enb.tx_batch(bad, d_out.data_ptr(), 1.0) != 0
+    finally:
+        enb.free()
+
+
+# ------------------------------------------------------------------ receive
+@pytest.mark.parametrize("c", SENT, ids=ids(SENT))
+def test_decode_host_and_batch_equal_reference(mods, c):
+    torch, _, PH, _, _ = mods
+    name, nre, n = c["name"], 12 * c["nof_prb"], sf_re(c)
+    sent = {(g, s): a for g, s, a in c["items"]}
+    ce = full(c, GOLD[name + "/ce"])
+    o = Obj(mods, c)
+    try:
+        grids = np.stack([full(c, GOLD[name + "/rx0"]), full(c, GOLD[name + "/rx1"])])  # subframes 0, 1
+        noise = [0.0, c["noise"]]
+        host = np.zeros((2, len(c["queries"]), 2), np.float32)
+        for v in range(2):
+            ref = GOLD[name + f"/ref{v}"]
+            dev, worst = c[f"dev{v}"], 0.0
+            for i, (g, s) in enumerate(c["queries"]):
+                r, ack, dist = o.ph.decode(c["tti"], g, s, grids[v], ce, noise[v])
+                assert r == 0
+                host[v, i] = ack, dist
+                bound = max(4.0 * dev, 1e-6 * max(1.0, abs(float(ref[i, 1]))))
+                worst = max(worst, abs(dist - float(ref[i, 1])))
+                if (g, s) in sent:
+                    assert ack == bool(ref[i, 0]) == bool(sent[(g, s)]), (v, g, s)
+                    assert abs(dist) >= 0.1
+                assert abs(dist - float(ref[i, 1])) <= bound, (v, g, s, dist, float(ref[i, 1]), bound)
+            print(f"{name}: receive variant {v} max |GPU - reference| of distance {worst:.3e} "
+                  f"(reference to float64 {dev:.3e})")
+        # the batch on device buffers: both subframes at once, the noise at a stride as srsran_ue_dl_gpu_last_ce's
+        d_g = to_dev(torch, grids)
+        d_ce = to_dev(torch, np.stack([ce, ce]))
+        d_noise = torch.tensor([noise[0], 9.0, 9.0, 9.0, noise[1], 9.0, 9.0, 9.0], dtype=torch.float32, device="cuda")
+        items = [(v, c["tti"], g, s) for v in range(2) for g, s in c["queries"]]
+        d_res = torch.zeros((len(items), 2), dtype=torch.float32, device="cuda")
+        assert o.ph.decode_batch(items, 2, d_g.data_ptr(), d_ce.data_ptr(), n, d_noise.data_ptr(), 4,
+                                 d_res.data_ptr()) == 0
+        torch.cuda.synchronize()
+        res = d_res.cpu().numpy().view(PH.RES_DTYPE).reshape(2, -1)
+        assert np.array_equal(res["ack_value"], host[:, :, 0].astype(np.uint32))
+        assert np.array_equal(bits(res["distance"]), bits(host[:, :, 1]))
+        # one-item calls: bit-identical
+        one = torch.zeros((1, 2), dtype=torch.float32, device="cuda")
+        for k in (0, len(items) // 2, len(items) - 1):
+            assert o.ph.decode_batch([items[k]], 2, d_g.data_ptr(), d_ce.data_ptr(), n, d_noise.data_ptr(), 4,
+                                     one.data_ptr()) == 0
+            torch.cuda.synchronize()
+            assert np.array_equal(one.cpu().numpy().view(np.uint32), d_res[k:k + 1].cpu().numpy().view(np.uint32))
+        # the one-row estimate form (read modulo the row): the fixture's channel is constant over the symbols
+        d_row = to_dev(torch, np.stack([ce, ce])[..., :nre])
+        d_res2 = torch.zeros((len(items), 2), dtype=torch.float32, device="cuda")
+        assert o.ph.decode_batch(items, 2, d_g.data_ptr(), d_row.data_ptr(), nre, d_noise.data_ptr(), 4,
+                                 d_res2.data_ptr()) == 0
+        torch.cuda.synchronize()
+        assert np.array_equal(d_res2.cpu().numpy().view(np.uint32), d_res.cpu().numpy().view(np.uint32))
+    finally:
+        o.free()
+
+
+# ------------------------------------------------------------------ eNB -> UE loop
+LOOP = [  # (nof_prb, ports, cp, phich_res, cell id, tti, cfi, [(n_prb_lowest, n_dmrs, ack)]: two share a group)
+    (25, 2, 0, 2, 301, 4, 2, [(0, 0, 1), (4, 0, 0), (5, 2, 1), (10, 0, 0)]),
+    (6, 1, 1, 3, 150, 9, 3, [(0, 0, 1), (1, 0, 0), (2, 0, 0), (3, 1, 1)]),
+]
+
+
+@pytest.mark.parametrize("case", LOOP, ids=["25prb_2p_norm", "6prb_1p_extcp"])
+def test_enb_put_phich_to_ue_decode_phich(mods, case):
+    torch, PD, PH, E, U = mods
+    nprb, P, cp, res, cell_id, tti, cfi, grants = case
+    rnti = 0x3C11
+    cell = U.cell(nprb, P, cell_id, phich_res=res, cp=cp)
+    N = U.lib().srsran_symbol_sz(nprb)
+    out = [np.zeros(15 * N, np.complex64) for _ in range(P)]
+    regs = PD.Regs(cell)
+    resources = [PH.calc(regs, cell, n, dm) for n, dm, _ in grants]
+    units = [g // 2 if cp else g for g, _ in resources]
+    assert len(set(resources)) == len(grants) and len(set(units)) < len(units)  # distinct, two in one unit
+    nof_cce = regs.q.pdcch_nregs[cfi - 1] // 9
+    enb = E.EnbDlRef(cell, out)
+    try:
+        du = PD.srsran_dci_ul_t()
+        du.rnti, du.format = rnti, PD.FORMAT0
+        du.type2_alloc.riv = 2 * nprb + 1  # 3 PRBs from PRB 1
+        du.tb.mcs_idx, du.tb.ndi, du.n_dmrs, du.freq_hop_fl = 9, True, 3, -1
+        locs = [loc for loc in PD.ue_locations(nof_cce, tti % 10, rnti) if (1 << loc[0]) <= nof_cce]
+        du.location.L, du.location.ncce = max(locs)
+        enb.put_base(U.sf_cfg(tti, cfi))
+        for n, dm, ack in grants:
+            enb.put_phich(n, dm, ack)
+        assert enb.put_pdcch_ul(U.srsran_dci_cfg_t(), du) == 0
+        enb.gen_signal()
+        grid = np.stack([enb.sf_symbols(p, sf_re(dict(cp=cp, nof_prb=nprb))) for p in range(P)])
+    finally:
+        enb.free()
+    re = regs.phich_re()
+    for u in set(units):
+        assert np.abs(grid[:, re[u]]).max() > 0  # the indicators are in the transmitted grid
+    rx = out[0] if P == 1 else out[0] + (0.8 + 0.3j) * out[1]
+    ue = U.UeDl(cell, 1)
+    o = None
+    try:
+        assert ue.fft_estimate([rx], tti, 0) == 0 and ue.last_cfi == cfi
+        assert ue.find_dl_dci(tti, cfi, rnti, tm=0 if P == 1 else 1) == []  # SRSRAN_TM1 / TM2
+        ul = ue.find_ul_dci(tti, cfi, rnti)
+        assert len(ul) == 1 and ul[0].n_dmrs == 3 and ul[0].tb.mcs_idx == 9  # the UL DCI is still found
+        got = [PH.ue_decode_phich(ue.q, U.sf_cfg(tti, cfi), ue.cfg, n, dm) for n, dm, _ in grants]
+        for (r, ack, dist), (_, _, sent) in zip(got, grants):
+            assert r == 0 and ack == bool(sent) and dist > 0.5, (r, ack, dist, sent)
+        # the same kernel on the same inputs: srsran_phich_decode on the UE object's grids and estimates
+        o = PH.Phich(cell, regs, 1)
+        g_ue, ce_ue = ue.grids(), ue.chest_res_ce()
+        for (g, s), (_, ack, dist) in zip(resources, got):
+            r2, ack2, dist2 = o.decode(tti, g, s, g_ue, ce_ue, float(ue.q.chest_res.noise_estimate))
+            assert r2 == 0 and ack2 == ack
+            assert np.float32(dist2).view(np.uint32) == np.float32(dist).view(np.uint32)
+    finally:
+        if o is not None:
+            o.free()
+        ue.free()
+        regs.free()

@@ -173,6 +173,32 @@ int srsran_pusch_gpu_decode_batch(srsran_pusch_t*              q,
                                   srsran_chest_ul_res_t*       chest_res,
                                   srsran_pusch_res_t*          res);
 
+/* ---- PUSCH transmit, UE side (pusch.h:78-118, pusch.c:178-181, 259-354; refsignal_ul.c:194-225) ---- */
+typedef struct {
+  uint8_t*           ptr;
+  srsran_uci_value_t uci;
+} srsran_pusch_data_t;
+
+/* As srsran_pusch_init_enb with is_ue = true; srsran_pusch_free / srsran_pusch_set_cell serve both sides. */
+int srsran_pusch_init_ue(srsran_pusch_t* q, uint32_t max_prb);
+/* pusch.c:259-354: the 64QAM limit (cfg->grant.tb.mod / nof_bits written back), the max_re check,
+ * srsran_pusch_assert_grant, srsran_ulsch_encode, scrambling with the placeholder / repetition rule, modulation,
+ * transform precoding and mapping.  sf_symbols: the host subframe grid of the cell; only the grant's data REs are
+ * written (pusch_cp): every other RE keeps its value, the DMRS symbols and the last symbol of a shortened subframe
+ * included.  L_prb must be 2^a 3^b 5^c (SRSRAN_ERROR_INVALID_INPUTS from srsran_pusch_assert_grant). */
+int srsran_pusch_encode(srsran_pusch_t*      q,
+                        srsran_ul_sf_cfg_t*  sf,
+                        srsran_pusch_cfg_t*  cfg,
+                        srsran_pusch_data_t* data,
+                        cf_t*                sf_symbols);
+/* srsran_refsignal_dmrs_pusch_put (refsignal_ul.c:194-225) for cell `cell`: r_pusch's two slot sequences
+ * (srsran_refsignal_dmrs_pusch_gen_cell, 2 * 12 * L_prb values) to symbol SRSRAN_REFSIGNAL_UL_L(slot, cp) of each
+ * slot at n_prb_tilde[slot] of the host grid sf_symbols. */
+int srsran_refsignal_dmrs_pusch_put_cell(const srsran_cell_t* cell,
+                                         srsran_pusch_cfg_t*  pusch_cfg,
+                                         cf_t*                r_pusch,
+                                         cf_t*                sf_symbols);
+
 #ifdef __cplusplus
 }
 #endif

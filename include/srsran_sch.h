@@ -483,6 +483,24 @@ int srsran_ulsch_gpu_decode_batch(srsran_sch_t*                q,
                                   float*                       d_avg_noi,
                                   void*                        stream);
 
+/* ---- UL-SCH transmit with UCI multiplexed (sch.c:1195-1337, uci.c:334-632) ----
+ * The CQI report (RM(32, O) up to 11 bits, CRC8 + tail-biting convolutional code + rate matching above), the
+ * UL-SCH TB (CRC, segmentation, turbo encoding, rate matching, from the bit offset Q'_CQI Qm of g, which need not be
+ * byte aligned), the channel interleaver with the RI cells skipped, then the RI and HARQ-ACK bits at their positions
+ * (placeholder and repetition bits are written as 0, as the reference writes them).  Host buffers; g_bits and q_bits
+ * are packed, MSB first: ceil((Q'_CQI + G) Qm / 8) and nof_bits / 8 bytes.  Returns (Q'_ACK + Q'_RI) Qm and writes
+ * cfg->K_segm.  Every call encodes from `data` at cfg->grant.tb.rv; cfg->softbuffers.tx is not used and data == NULL
+ * with tbs > 0 returns SRSRAN_ERROR (as documented for srsran_dlsch_encode).  tbs == 0 carries UCI only (the beta
+ * offsets divided by beta_CQI, sch.c:1245, 1302).  Filler bits and an RI of more than two bits are refused.  The UCI
+ * coding runs on the host (a few dozen bits); the TB and the multiplexing run on the GPU (enc_kernel.hip,
+ * pusch_tx_kernel.hip). */
+int srsran_ulsch_encode(srsran_sch_t*       q,
+                        srsran_pusch_cfg_t* cfg,
+                        uint8_t*            data,
+                        srsran_uci_value_t* uci_data,
+                        uint8_t*            g_bits,
+                        uint8_t*            q_bits);
+
 #ifdef __cplusplus
 }
 #endif

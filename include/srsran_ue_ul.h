@@ -1,0 +1,163 @@
+/*
+ * include/srsran_ue_ul.h -- MI355X UE uplink transmit (PUSCH branch) as a C-ABI drop-in.
+ *
+ * Replaces, with the reference's names, argument meaning and return codes:
+ *   srsran_ue_ul_powerctrl_t, srsran_ul_cfg_t, srsran_ue_ul_normalize_mode_t, srsran_ue_ul_cfg_t
+ *                                            lib/include/srsran/phy/ue/ue_ul.h:49-92
+ *   srsran_refsignal_srs_cfg_t               lib/include/srsran/phy/ch_estimation/refsignal_ul.h:53-70
+ *   srsran_pusch_hopping_cfg_t               lib/include/srsran/phy/phch/pusch_cfg.h:35-42
+ *   srsran_ue_ul_t, srsran_ue_ul_init / free / set_cell / encode
+ *                                            lib/include/srsran/phy/ue/ue_ul.h:94-142, lib/src/phy/ue/ue_ul.c:41-175, 246-351,
+ *                                            618-659
+ * with srsran_pusch_init_ue / srsran_pusch_encode / srsran_refsignal_dmrs_pusch_put_cell (srsran_pusch.h) and
+ * srsran_ulsch_encode (srsran_sch.h) underneath.
+ *
+ * srsran_ue_ul_encode with a grant: the grid zeroed, srsran_pusch_encode, the DMRS put, SC-FDMA modulation
+ * (freq_shift_f = 0.5, normalize = true, the cell's CP), apply_cfo, apply_norm -- all on the GPU
+ * (csrc/pusch_tx_kernel.hip, csrc/ofdm_kernel.hip); q->out_buffer (host) receives the subframe's samples.
+ * srsran_ue_ul_gpu_tx_batch (added) does the same for many UEs of one or more cells on device buffers.
+ *
+ * Not provided (SRSRAN_ERROR with a message): the PUCCH and SRS-only branches of srsran_ue_ul_encode, an SRS
+ * configured for transmission in the subframe (srs_tx_enabled, ue_ul.c:453-462; every other subframe is encoded),
+ * srsran_ue_ul_pregen_signals, srsran_ue_ul_set_cfr, a grant whose L_prb is not 2^a 3^b 5^c, filler bits.  srsran_ue_ul_dci_to_pusch_grant, srsran_ue_ul_pusch_hopping and the power
+ * helpers are not declared: the caller supplies the grant with n_prb_tilde set, as for the receive side.
+ */
+#ifndef SRSRAN_AMD_UE_UL_H
+#define SRSRAN_AMD_UE_UL_H
+
+#include <stdbool.h>
+#include <stdint.h>
+
+#include "srsran_pucch.h"
+#include "srsran_pusch.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SRSRAN_SF_LEN(symbol_sz) ((symbol_sz) * 15)                                /* phy_common.h:134 */
+#define SRSRAN_SF_LEN_PRB(nof_prb) ((uint32_t)SRSRAN_SF_LEN(srsran_symbol_sz(nof_prb))) /* phy_common.h:138 */
+
+/* SRS configuration: data only (no SRS is generated) */
+typedef struct {
+  uint32_t subframe_config;
+  uint32_t bw_cfg;
+  bool     simul_ack;
+  uint32_t B;
+  uint32_t b_hop;
+  uint32_t n_srs;
+  uint32_t I_srs;
+  uint32_t k_tc;
+  uint32_t n_rrc;
+  bool     dedicated_enabled;
+  bool     common_enabled;
+  bool     configured;
+} srsran_refsignal_srs_cfg_t;
+
+/* PUSCH hopping configuration: data only (the caller computes n_prb_tilde) */
+typedef struct {
+  enum { SRSRAN_PUSCH_HOP_MODE_INTER_SF = 1, SRSRAN_PUSCH_HOP_MODE_INTRA_SF = 0 } hop_mode;
+  uint32_t hopping_offset;
+  uint32_t n_sb;
+  uint32_t n_rb_ho;
+  uint32_t current_tx_nb;
+  bool     hopping_enabled;
+} srsran_pusch_hopping_cfg_t;
+
+/* UE UL power control: data only */
+typedef struct {
+  float p0_nominal_pusch;
+  float alpha;
+  float p0_nominal_pucch;
+  float delta_f_pucch[5];
+  float delta_preamble_msg3;
+  float p0_ue_pusch;
+  bool  delta_mcs_based;
+  bool  acc_enabled;
+  float p0_ue_pucch;
+  float p_srs_offset;
+} srsran_ue_ul_powerctrl_t;
+
+typedef struct {
+  srsran_pucch_cfg_t                pucch;
+  srsran_pusch_cfg_t                pusch;
+  srsran_pusch_hopping_cfg_t        hopping;
+  srsran_ue_ul_powerctrl_t          power_ctrl;
+  srsran_refsignal_dmrs_pusch_cfg_t dmrs;
+  srsran_refsignal_srs_cfg_t        srs;
+} srsran_ul_cfg_t;
+
+typedef enum {
+  SRSRAN_UE_UL_NORMALIZE_MODE_AUTO = 0,
+  SRSRAN_UE_UL_NORMALIZE_MODE_FORCE_AMPLITUDE
+} srsran_ue_ul_normalize_mode_t;
+
+typedef struct {
+  srsran_ul_cfg_t               ul_cfg;
+  bool                          grant_available;
+  uint32_t                      cc_idx;
+  srsran_ue_ul_normalize_mode_t normalize_mode;
+  float                         force_peak_amplitude;
+  bool                          cfo_en;
+  float                         cfo_tol; /* not used: every call rotates by cfo_value, as srsran_vec_apply_cfo */
+  float                         cfo_value;
+} srsran_ue_ul_cfg_t;
+
+/* The object keeps the reference's members that this library has (ue_ul.h:94-118); the pregenerated signals, the
+ * PUCCH object, the hopping sequence and the CFR configuration have no counterpart. */
+typedef struct {
+  srsran_cell_t  cell;
+  bool           signals_pregenerated; /* always false */
+  srsran_ofdm_t  fft;
+  srsran_pusch_t pusch;
+  cf_t*          out_buffer;
+  void*          gpu; /* added: device grid / sample staging, the cell's DMRS hopping tables, the CFO table */
+} srsran_ue_ul_t;
+
+int  srsran_ue_ul_init(srsran_ue_ul_t* q, cf_t* out_buffer, uint32_t max_prb);
+void srsran_ue_ul_free(srsran_ue_ul_t* q);
+int  srsran_ue_ul_set_cell(srsran_ue_ul_t* q, srsran_cell_t cell);
+/* not provided: SRSRAN_ERROR */
+int srsran_ue_ul_set_cfr(srsran_ue_ul_t* q, const void* cfr);
+int srsran_ue_ul_pregen_signals(srsran_ue_ul_t* q, srsran_ue_ul_cfg_t* cfg);
+
+/* ue_ul.c:618-659: 1 when a subframe was generated, 0 when there is nothing to send (out_buffer zeroed), -1 on
+ * error.  data->ptr: the host payload. */
+int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_cfg_t* cfg, srsran_pusch_data_t* data);
+
+/* ---- added: many UE subframes of one or more cells, asynchronous on `stream` ----
+ * Every stage (TB CRC, code blocks, multiplexing + scrambling + mapping, transform precoding + DMRS, normalisation)
+ * is one launch over all entries; the OFDM modulation is one launch pair per cell object, the CFO product one launch
+ * per entry that enables it.  Results are bit-identical to single-entry calls in any order and composition.
+ * The transmit scratch of entries[0].q serves the whole batch, and every object keeps device state between calls (its
+ * grids, samples and the CFO phasor table): use one stream per object, one batch at a time, in stream order.  The
+ * descriptors are uploaded from pageable host memory, so the call returns once they are staged, not before.
+ * Entries must have grant_available; cfg->ul_cfg.pusch is updated as srsran_pusch_encode updates it. */
+typedef struct {
+  srsran_ue_ul_t*           q;      /* the entry's cell (srsran_ue_ul_set_cell done) */
+  srsran_ul_sf_cfg_t*       sf;
+  srsran_ue_ul_cfg_t*       cfg;
+  const srsran_uci_value_t* uci;    /* may be NULL without UCI */
+  const uint8_t*            d_data; /* device payload, tbs / 8 bytes (may be NULL with tbs == 0) */
+  cf_t*                     d_out;  /* device, SRSRAN_SF_LEN_PRB(cell.nof_prb) samples; NULL: grid only */
+  cf_t*                     d_grid; /* device, optional: the subframe grid, 2 N_symb x 12 nof_prb REs */
+} srsran_ue_ul_gpu_entry_t;
+
+int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* entries, void* stream);
+
+/* added, read-only: device pointers to the last encode on this object (the last batch entry naming it): the packed
+ * scrambled bits (nof_bits / 8 bytes), the modulation symbols (nof_re) and the subframe grid (nof_grid REs).
+ * Valid until the next encode on the object or on the object whose scratch served the batch; SRSRAN_ERROR before
+ * the first. */
+int srsran_ue_ul_gpu_last(srsran_ue_ul_t* q,
+                          const uint8_t** d_scrambled,
+                          uint32_t*       nof_bits,
+                          const cf_t**    d_symbols,
+                          uint32_t*       nof_re,
+                          const cf_t**    d_grid,
+                          uint32_t*       nof_grid);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -26,38 +26,15 @@
 #include "eq_dev.h"
 #include "gmem.h"
 #include "llr_kernel.h"
+#include "seq_mod_dev.h"
 #include "stage_timing.h"
 
 namespace srsran_amd {
 
-static constexpr int GOLD_NC   = 1600;  // sequence.c:39
-static constexpr int JUMP_BITS = 24;    // offsets below 2^24 bits
-static constexpr int JUMP_LVLS = 3;     // offset = b0 + 256 b1 + 65536 b2
 static constexpr int GOLD_LANE_SYMBOLS = 4 * LLR_SPT_CFG;  // symbols whose sequence bits one lane of the first wave steps out
 static constexpr int GOLD_NMOD         = 5;   // BPSK .. 256QAM: Qm = 1, 2, 4, 6, 8
 
-struct GoldTables {
-  uint32_t        x1_nc;      // x1 after Nc steps from x1 = 1
-  uint32_t        x2_nc[31];  // x2 after Nc steps from the unit seed 1 << i
-  const uint32_t* jump;       // [lvl][b][lfsr][32]: columns of A_lfsr^(b * 256^lvl) (device memory)
-  const uint32_t* stride;     // [MOD][lane][lfsr][32]: columns of A_lfsr^(lane * GOLD_LANE_SYMBOLS * Qm) (device)
-};
 __constant__ GoldTables kGold;
-
-__host__ __device__ inline uint32_t step_x1(uint32_t s) { return (s >> 1) ^ (((s ^ (s >> 3)) & 1u) << 30); }
-__host__ __device__ inline uint32_t step_x2(uint32_t s)
-{
-  return (s >> 1) ^ (((s ^ (s >> 1) ^ (s >> 2) ^ (s >> 3)) & 1u) << 30);
-}
-__host__ __device__ inline uint32_t apply(const uint32_t* cols, uint32_t v)
-{
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 0; i < 31; i++) {
-    r ^= ((v >> i) & 1u) ? cols[i] : 0u;
-  }
-  return r;
-}
 
 hipError_t gold_tables_init()
 {
@@ -151,22 +128,10 @@ hipError_t gold_tables_init()
   return err;
 }
 
-// columns (32 dwords, 16-byte aligned) applied to v
-__device__ __forceinline__ uint32_t apply_cols(const uint32_t* __restrict__ cols, uint32_t v)
+hipError_t gold_tables_get(GoldTables* out)
 {
-  const uint4* c4 = reinterpret_cast<const uint4*>(cols);
-  uint32_t     r  = 0;
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    const uint4 c = c4[q];
-    r ^= ((v >> (4 * q)) & 1u) ? c.x : 0u;
-    r ^= ((v >> (4 * q + 1)) & 1u) ? c.y : 0u;
-    r ^= ((v >> (4 * q + 2)) & 1u) ? c.z : 0u;
-    if (q < 7) {
-      r ^= ((v >> (4 * q + 3)) & 1u) ? c.w : 0u;
-    }
-  }
-  return r;
+  const hipError_t e = gold_tables_init();
+  return e != hipSuccess ? e : hipMemcpyFromSymbol(out, HIP_SYMBOL(kGold), sizeof(*out));
 }
 
 // LFSR states at bit offset `off` (< 2^24) of the sequence for `seed`: three table jumps.
@@ -305,8 +270,6 @@ __device__ __forceinline__ void demap(float re, float im, uint32_t i, uint32_t n
 static constexpr int LLR_THREADS = 256;
 static constexpr int SPT         = LLR_SPT_CFG;  // symbols per thread
 static_assert(LLR_THREADS * SPT == LLR_BLOCK_SYMBOLS, "llr_kernel.h block size");
-
-__device__ __forceinline__ float2 modulate(int mod, uint32_t i);
 
 // csi_correction (pdsch.c:523-618, SSE build) for the LLRs o[0..Q) of symbol s:
 // symbols inside the SSE blocks get mulhi(e, cvtps_pi16(csi * 32767/csi_max)) -- with the
@@ -447,19 +410,6 @@ __device__ __forceinline__ void csi_correct8(int8_t* o, float cs, float mx)
   for (int b = 0; b < Qm<MOD>::v; b++) {
     o[b] = wrap8(cvt_tz((float)o[b] * c));
   }
-}
-
-// advance both LFSRs by 16 bits and return c(n..n+15) (bit k = c(n+k)): the recurrences
-// x1(m+31) = x1(m+3) ^ x1(m) and x2(m+31) = x2(m+3) ^ x2(m+2) ^ x2(m+1) ^ x2(m) give 28 new bits
-// per shift-xor, 16 of which are used
-__device__ __forceinline__ uint32_t gold16(uint32_t& x1, uint32_t& x2)
-{
-  const uint32_t c  = (x1 ^ x2) & 0xFFFFu;
-  const uint32_t n1 = ((x1 >> 3) ^ x1) & 0xFFFFu;
-  const uint32_t n2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 0xFFFFu;
-  x1                = (x1 >> 16) | (n1 << 15);
-  x2                = (x2 >> 16) | (n2 << 15);
-  return c;
 }
 
 // The fused path's symbols: the NL layers of REs base + t + (r0 + u) LLR_THREADS, u < U, equalised from the received
@@ -1082,40 +1032,6 @@ hipError_t seq_unpack_launch(uint8_t* d_out, uint32_t len, uint32_t seed, hipStr
 }
 
 // ---------------------------------------------------------------- transmitter
-// modulation tables of lte_tables.c:45-160, as the same float expressions
-__device__ __forceinline__ float qam64_level(uint32_t hi, uint32_t lo)  // (b2, b4) -> 3, 1, 5, 7 / sqrt(42)
-{
-  const uint32_t m = hi * 2 + lo;
-  return m == 0 ? 3.0f / sqrtf(42.0f) : m == 1 ? 1.0f / sqrtf(42.0f) : m == 2 ? 5.0f / sqrtf(42.0f) : 7.0f / sqrtf(42.0f);
-}
-
-// symbol of modulation `mod` (1 QPSK, 2 16QAM, 3 64QAM, 4 256QAM) from its Qm bits, b0 first (MSB)
-__device__ __forceinline__ float2 modulate(int mod, uint32_t i)
-{
-  if (mod == 1) {
-    const float l = (float)0.70710678118654752440;  // M_SQRT1_2
-    return make_float2((i & 2u) ? -l : l, (i & 1u) ? -l : l);
-  }
-  if (mod == 2) {
-    const float l1 = 1.0f / sqrtf(10.0f), l2 = 3.0f / sqrtf(10.0f);
-    const float re = (i & 2u) ? l2 : l1, im = (i & 1u) ? l2 : l1;
-    return make_float2((i & 8u) ? -re : re, (i & 4u) ? -im : im);
-  }
-  if (mod == 3) {
-    const float re = qam64_level((i >> 3) & 1u, (i >> 1) & 1u), im = qam64_level((i >> 2) & 1u, i & 1u);
-    return make_float2((i & 32u) ? -re : re, (i & 16u) ? -im : im);
-  }
-  float offset = -1, re = 0, im = 0;  // set_256QAMtable's loop
-  for (uint32_t j = 0; j < 4; j++) {
-    re += offset;
-    im += offset;
-    offset *= 2;
-    re *= (i & (1u << (2 * j + 1))) ? +1 : -1;
-    im *= (i & (1u << (2 * j + 0))) ? +1 : -1;
-  }
-  return make_float2(re / sqrtf(170), im / sqrtf(170));
-}
-
 static constexpr int TX_SPT = 16;  // symbols a thread (a whole number of bytes of e bits for every Qm)
 
 // bits of TX_SPT symbols of one codeword starting at symbol k0: scrambled (sequences.c pdsch seed,

@@ -1,4 +1,5 @@
-// srsran_4g_amd/csrc/pusch_api.cpp -- C-ABI of the PUSCH receive path (include/srsran_pusch.h):
+// srsran_4g_amd/csrc/pusch_api.cpp -- C-ABI of the PUSCH receive path (include/srsran_pusch.h) and, at the end, of
+// the UE's PUSCH transmit path (srsran_pusch_encode, include/srsran_ue_ul.h):
 // PUSCH DMRS generation (refsignal_ul.c:95-358 restated), the UL channel estimator object
 // (chest_ul.c:53-433) and srsran_pusch_t (pusch.c:108-471), over the kernels of pusch_kernel.hip,
 // llr_kernel.hip and the UL-SCH decoder of sch_api.cpp.
@@ -12,8 +13,11 @@
 #include <vector>
 
 #include "../../include/srsran_pusch.h"
+#include "../../include/srsran_ue_ul.h"
 #include "llr_kernel.h"
+#include "ofdm_kernel.h"
 #include "pusch_kernel.h"
+#include "pusch_tx_internal.h"
 #include "ulsch_batch.h"
 
 namespace srsran_amd {
@@ -297,6 +301,10 @@ struct PuschGpu {
   uint8_t*    d_data = nullptr;  // batch: decoded TBs of the UEs without UCI
   size_t      data_cap = 0;
   uint32_t    last_nsym = 0, last_nllr = 0;  // the last host-sync decode's counts (srsran_pusch_gpu_last_soft)
+  uint8_t*    d_tx   = nullptr;  // transmit: descriptors and DMRS values of a batch
+  size_t      tx_cap = 0;
+  uint8_t*    d_txdata = nullptr;  // transmit (sync API): the payload
+  size_t      txdata_cap = 0;
 };
 
 uint32_t pusch_seed(uint16_t rnti, uint32_t nslot, uint32_t cell_id)  // sequences.c:119-122
@@ -672,6 +680,8 @@ void srsran_pusch_free(srsran_pusch_t* q)
     hipFree(g->d_bce);
     hipFree(g->d_g);
     hipFree(g->d_data);
+    hipFree(g->d_tx);
+    hipFree(g->d_txdata);
     delete g;
   }
   srsran_sch_free(&q->ul_sch);
@@ -1003,6 +1013,566 @@ int srsran_pusch_gpu_decode_batch(srsran_pusch_t*              q,
     }
   }
   return rc;
+}
+
+}  // extern "C"
+
+// ---------------- PUSCH transmit (pusch.c:178-181, 259-354) and the UE uplink (ue_ul.c) ----------------
+namespace {
+
+// One transmission of a batch: the PUSCH object of its cell, where its grid goes and, for the UE uplink path, the
+// DMRS tables and the normalisation of its samples.
+struct TxReq {
+  srsran_pusch_t*                          pusch;
+  const UlHopping*                         hop;  // DMRS put (null: none)
+  const srsran_refsignal_dmrs_pusch_cfg_t* dmrs_cfg;
+  srsran_ul_sf_cfg_t*                      sf;
+  srsran_pusch_cfg_t*                      cfg;
+  const srsran_uci_value_t*                uci;
+  const uint8_t*                           d_data;
+  float2*                                  d_grid;
+  bool                                     zero_rest;
+  const float2*                            samples_in;  // null: no normalisation stage
+  float2*                                  samples_out;
+  uint32_t                                 sf_len, norm_mode;
+  float                                    norm_factor, force_peak;
+};
+
+// srsran_pusch_encode for n transmissions up to the grids: checks, the UL-SCH step, then one multiplexing launch and
+// one transform-precoding launch over the batch.  desc / *d_desc: the descriptors (host copy, device array in
+// owner's scratch) for the caller's later stages.  Nothing is launched when a transmission is refused.
+int pusch_tx_run(srsran_pusch_t* owner, uint32_t n, const TxReq* r, std::vector<PuschTxUe>& desc,
+                 const PuschTxUe** d_desc, hipStream_t st)
+{
+  PuschGpu* g = (PuschGpu*)owner->gpu;
+  desc.assign(n, PuschTxUe{});
+  std::vector<UlschTxJob> jobs(n);
+  std::vector<cf_t>       dmrs;
+  std::vector<size_t>     dmrs_off(n, 0);
+  uint32_t                max_H = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    srsran_pusch_t*     q   = r[i].pusch;
+    srsran_pusch_cfg_t* cfg = r[i].cfg;
+    if (!q || !q->gpu || !cfg || !r[i].sf || !r[i].d_grid) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    limit_64qam(cfg);
+    if (cfg->grant.nof_re > q->max_re) {
+      fprintf(stderr, "[srsran_pusch] Error too many RE per subframe (%u). PUSCH configured for %u RE (%u PRB)\n",
+              cfg->grant.nof_re, q->max_re, q->cell.nof_prb);
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    const int err = srsran_pusch_assert_grant(&cfg->grant);
+    if (err != SRSRAN_SUCCESS) {
+      return err;
+    }
+    if (check_alloc(q->cell, cfg) != SRSRAN_SUCCESS) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    PuschTxUe&     u = desc[i];
+    const uint32_t L = cfg->grant.L_prb, M = L * SRSRAN_NRE;
+    u.nof_symb       = data_symbols(q->cell.cp, r[i].sf->shortened, u.data_sym);
+    if (u.nof_symb * M != cfg->grant.nof_re) {
+      fprintf(stderr, "[srsran_pusch] Error trying to allocate %u symbols but %u were allocated (tti=%u, short=%d, L=%u)\n",
+              cfg->grant.nof_re, u.nof_symb * M, r[i].sf->tti, (int)r[i].sf->shortened, L);
+      return SRSRAN_ERROR;
+    }
+    const uint32_t Qm = srsran_mod_bits_x_symbol(cfg->grant.tb.mod);
+    PuschUe        plan;
+    if (Qm == 0 || cfg->grant.tb.nof_bits != cfg->grant.nof_re * Qm || cfg->grant.nof_symb != u.nof_symb ||
+        !dft_plan(M, plan)) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    memcpy(u.radix, plan.radix, sizeof(u.radix));
+    u.nstages    = plan.nstages;
+    u.grid       = r[i].d_grid;
+    u.ncell_re   = q->cell.nof_prb * SRSRAN_NRE;
+    u.M          = M;
+    u.nsym_slot  = nsymb_slot(q->cell.cp);
+    u.n_tilde[0] = cfg->grant.n_prb_tilde[0];
+    u.n_tilde[1] = cfg->grant.n_prb_tilde[1];
+    u.dft_norm   = 1.0f / sqrtf((float)M);
+    u.zero_rest  = r[i].zero_rest;
+    u.seed       = pusch_seed(cfg->rnti, 2 * (r[i].sf->tti % SRSRAN_NOF_SF_X_FRAME), q->cell.id);
+    u.samples_in  = r[i].samples_in;
+    u.samples_out = r[i].samples_out;
+    u.sf_len      = r[i].sf_len;
+    u.norm_mode   = r[i].norm_mode;
+    u.norm_factor = r[i].norm_factor;
+    u.force_peak  = r[i].force_peak;
+    if (r[i].hop) {
+      u.put_dmrs  = 1;
+      dmrs_off[i] = dmrs.size();
+      dmrs.resize(dmrs.size() + 2 * M);
+      if (dmrs_gen(q->cell, *r[i].hop, *r[i].dmrs_cfg, L, r[i].sf->tti % SRSRAN_NOF_SF_X_FRAME, cfg->grant.n_dmrs,
+                   dmrs.data() + dmrs_off[i]) != SRSRAN_SUCCESS) {
+        fprintf(stderr, "[srsran_ue_ul] Error generating PUSCH DMRS signals\n");
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
+    }
+    jobs[i] = {cfg, r[i].uci, r[i].d_data, false, false, 0};
+    max_H   = std::max(max_H, cfg->grant.nof_re);
+  }
+  if (ulsch_tx_prepare(&owner->ul_sch, n, jobs.data(), desc.data(), st) != SRSRAN_SUCCESS) {
+    fprintf(stderr, "[srsran_pusch] Error encoding TB\n");
+    return SRSRAN_ERROR;
+  }
+  const size_t o_dmrs = (n * sizeof(PuschTxUe) + 15) & ~(size_t)15;
+  if (!grow((void**)&g->d_tx, &g->tx_cap, o_dmrs + dmrs.size() * sizeof(cf_t))) {
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    desc[i].dmrs = (const float2*)(g->d_tx + o_dmrs) + dmrs_off[i];
+  }
+  *d_desc = (const PuschTxUe*)g->d_tx;
+  if (hipMemcpyAsync(g->d_tx, desc.data(), n * sizeof(PuschTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
+      (!dmrs.empty() && hipMemcpyAsync(g->d_tx + o_dmrs, dmrs.data(), dmrs.size() * sizeof(cf_t), hipMemcpyHostToDevice,
+                                       st) != hipSuccess) ||
+      pusch_tx_mux_launch(*d_desc, n, max_H, st) != hipSuccess || pusch_tx_grid_launch(*d_desc, n, st) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// ---------------- ue_ul device state ----------------
+struct UeUlGpu {
+  UlHopping hop;
+  bool      hop_ok = false;
+  float2*   d_grid = nullptr;  // the grids of this object's entries of a batch
+  size_t    grid_cap = 0;
+  float2*   d_samp = nullptr;  // their samples before the normalisation
+  size_t    samp_cap = 0;
+  float2*   d_cfo = nullptr;   // srsran_vec_apply_cfo's phasors of cfo_freq (cfo_len samples)
+  size_t    cfo_cap = 0;
+  float     cfo_freq = 0.0f;
+  uint32_t  cfo_len = 0;
+  uint8_t*  d_io = nullptr;    // sync API: payload, then the output samples
+  size_t    io_cap = 0;
+  // srsran_ue_ul_gpu_last
+  const uint8_t* last_s = nullptr;
+  const float2*  last_d = nullptr;
+  const float2*  last_grid = nullptr;
+  uint32_t       last_bits = 0, last_re = 0, last_ngrid = 0;
+};
+
+// srs_tx_enabled (ue_ul.c:453-462): the subframe carries this UE's SRS when it is a cell-specific SRS subframe
+// (srsran_refsignal_srs_send_cs, refsignal_ul.c:703-749, 36.211 Table 5.5.3.3-1) and a UE-specific one
+// (srsran_refsignal_srs_send_ue, refsignal_ul.c:560-622, 36.213 Table 8.2-1).  SRS is not generated: such a subframe
+// is refused, every other one is encoded as the reference encodes it.
+bool srs_send_cs(uint32_t subframe_config, uint32_t sf_idx)
+{
+  static const uint32_t T_sfc[15] = {1, 2, 2, 5, 5, 5, 5, 5, 5, 10, 10, 10, 10, 10, 10};
+  static const uint32_t Delta_sfc1[7] = {0, 0, 1, 0, 1, 2, 3}, Delta_sfc2[4] = {0, 1, 2, 3};
+  if (subframe_config >= 15 || sf_idx >= 10) {
+    return false;
+  }
+  const uint32_t m = sf_idx % T_sfc[subframe_config];
+  if (subframe_config < 7) {
+    return m == Delta_sfc1[subframe_config];
+  } else if (subframe_config == 7) {
+    return m == 0 || m == 1;
+  } else if (subframe_config == 8) {
+    return m == 2 || m == 3;
+  } else if (subframe_config < 13) {
+    return m == Delta_sfc2[subframe_config - 9];
+  } else if (subframe_config == 13) {
+    return !(m == 5 || m == 7 || m == 9);
+  }
+  return !(m == 7 || m == 9);
+}
+
+bool srs_send_ue(uint32_t I_srs, uint32_t tti)
+{
+  static const uint32_t first[9] = {0, 2, 7, 17, 37, 77, 157, 317, 637}, T_srs[8] = {2, 5, 10, 20, 40, 80, 160, 320};
+  if (I_srs >= 637 || tti >= 10240) {
+    return false;
+  }
+  uint32_t k = 0;
+  while (I_srs >= first[k + 1]) {
+    k++;
+  }
+  return (tti - (I_srs - first[k])) % T_srs[k] == 0;  // unsigned, as the reference's (tti - Toffset) % T_srs
+}
+
+bool srs_in_subframe(const srsran_ue_ul_cfg_t* cfg, uint32_t tti)
+{
+  const srsran_refsignal_srs_cfg_t& srs = cfg->ul_cfg.srs;
+  if (srs.configured && srs_send_cs(srs.subframe_config, tti % 10) && srs_send_ue(srs.I_srs, tti)) {
+    fprintf(stderr, "[srsran_ue_ul] SRS transmission is not provided (tti %u carries this UE's SRS)\n", tti);
+    return true;
+  }
+  return false;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srsran_pusch_init_ue(srsran_pusch_t* q, uint32_t max_prb)
+{
+  const int ret = srsran_pusch_init_enb(q, max_prb);
+  if (ret == SRSRAN_SUCCESS) {
+    q->is_ue = true;
+  }
+  return ret;
+}
+
+int srsran_pusch_encode(srsran_pusch_t*      q,
+                        srsran_ul_sf_cfg_t*  sf,
+                        srsran_pusch_cfg_t*  cfg,
+                        srsran_pusch_data_t* data,
+                        cf_t*                sf_symbols)
+{
+  if (!q || !q->gpu || !cfg || !sf || !data || !sf_symbols) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  PuschGpu*      g      = (PuschGpu*)q->gpu;
+  hipStream_t    st     = sch_stream(&q->ul_sch);
+  const size_t   sf_re  = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
+  const uint32_t nbytes = cfg->grant.tb.tbs > 0 ? (uint32_t)cfg->grant.tb.tbs / 8 : 0;
+  if (nbytes && !data->ptr) {
+    fprintf(stderr, "[srsran_pusch] encoding from the soft buffer (data == NULL) is not provided\n");
+    return SRSRAN_ERROR;
+  }
+  if (sf_re == 0 || !grow((void**)&g->d_grid, &g->grid_cap, sf_re * sizeof(float2)) ||
+      !grow((void**)&g->d_txdata, &g->txdata_cap, (size_t)nbytes + 16) ||
+      hipMemcpyAsync(g->d_grid, sf_symbols, sf_re * sizeof(float2), hipMemcpyHostToDevice, st) != hipSuccess ||
+      (nbytes && hipMemcpyAsync(g->d_txdata, data->ptr, nbytes, hipMemcpyHostToDevice, st) != hipSuccess)) {
+    return SRSRAN_ERROR;
+  }
+  TxReq r;
+  memset(&r, 0, sizeof(r));
+  r.pusch  = q;
+  r.sf     = sf;
+  r.cfg    = cfg;
+  r.uci    = &data->uci;
+  r.d_data = nbytes ? g->d_txdata : nullptr;
+  r.d_grid = g->d_grid;
+  std::vector<PuschTxUe> desc;
+  const PuschTxUe*       d_desc = nullptr;
+  int                    ret    = pusch_tx_run(q, 1, &r, desc, &d_desc, st);
+  if (ret == SRSRAN_SUCCESS &&
+      hipMemcpyAsync(sf_symbols, g->d_grid, sf_re * sizeof(float2), hipMemcpyDeviceToHost, st) != hipSuccess) {
+    ret = SRSRAN_ERROR;
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    ret = SRSRAN_ERROR;
+  }
+  return ret;
+}
+
+int srsran_refsignal_dmrs_pusch_put_cell(const srsran_cell_t* cell,
+                                         srsran_pusch_cfg_t*  pusch_cfg,
+                                         cf_t*                r_pusch,
+                                         cf_t*                sf_symbols)
+{
+  if (!cell || !pusch_cfg || !r_pusch || !sf_symbols || !cell_valid(*cell) ||
+      check_alloc(*cell, pusch_cfg) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  const uint32_t M = pusch_cfg->grant.L_prb * SRSRAN_NRE;
+  for (uint32_t ns = 0; ns < 2; ns++) {
+    const uint32_t L = SRSRAN_REFSIGNAL_UL_L(ns, cell->cp);
+    memcpy(sf_symbols + (size_t)L * cell->nof_prb * SRSRAN_NRE + pusch_cfg->grant.n_prb_tilde[ns] * SRSRAN_NRE,
+           r_pusch + ns * M, M * sizeof(cf_t));
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// ---------------- ue_ul.c:41-175 ----------------
+int srsran_ue_ul_init(srsran_ue_ul_t* q, cf_t* out_buffer, uint32_t max_prb)
+{
+  if (!q) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  memset(q, 0, sizeof(*q));
+  srsran_ofdm_cfg_t ofdm_cfg;
+  memset(&ofdm_cfg, 0, sizeof(ofdm_cfg));
+  ofdm_cfg.nof_prb      = max_prb;
+  ofdm_cfg.cp           = SRSRAN_CP_NORM;
+  ofdm_cfg.freq_shift_f = 0.5f;
+  ofdm_cfg.normalize    = true;
+  if (srsran_ofdm_tx_init_cfg(&q->fft, &ofdm_cfg)) {
+    fprintf(stderr, "[srsran_ue_ul] Error initiating FFT\n");
+    return SRSRAN_ERROR;
+  }
+  if (srsran_pusch_init_ue(&q->pusch, max_prb)) {
+    fprintf(stderr, "[srsran_ue_ul] Error creating PUSCH object\n");
+    srsran_ofdm_tx_free(&q->fft);
+    return SRSRAN_ERROR;
+  }
+  q->gpu        = new UeUlGpu();
+  q->out_buffer = out_buffer;
+  return SRSRAN_SUCCESS;
+}
+
+void srsran_ue_ul_free(srsran_ue_ul_t* q)
+{
+  if (!q) {
+    return;
+  }
+  UeUlGpu* g = (UeUlGpu*)q->gpu;
+  if (g) {
+    hipStream_t st = sch_stream(&q->pusch.ul_sch);
+    if (st) {
+      hipStreamSynchronize(st);
+    }
+    hipFree(g->d_grid);
+    hipFree(g->d_samp);
+    hipFree(g->d_cfo);
+    hipFree(g->d_io);
+    delete g;
+  }
+  srsran_ofdm_tx_free(&q->fft);
+  srsran_pusch_free(&q->pusch);
+  memset(q, 0, sizeof(*q));
+}
+
+int srsran_ue_ul_set_cell(srsran_ue_ul_t* q, srsran_cell_t cell)
+{
+  if (!q || !q->gpu || !cell_valid(cell)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (q->cell.id != cell.id || q->cell.nof_prb == 0) {
+    UeUlGpu* g = (UeUlGpu*)q->gpu;
+    g->hop_ok  = false;
+    g->last_bits = 0;
+    if (srsran_ofdm_rx_set_prb(&q->fft, cell.cp, cell.nof_prb)) {  // srsran_ofdm_tx_set_prb: the same object
+      fprintf(stderr, "[srsran_ue_ul] Error resizing FFT\n");
+      return SRSRAN_ERROR;
+    }
+    if (srsran_pusch_set_cell(&q->pusch, cell)) {
+      return SRSRAN_ERROR;
+    }
+    q->cell = cell;
+    hopping_tables(cell, g->hop);
+    g->hop_ok = true;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_ue_ul_set_cfr(srsran_ue_ul_t*, const void*)
+{
+  fprintf(stderr, "[srsran_ue_ul] crest factor reduction is not provided\n");
+  return SRSRAN_ERROR;
+}
+
+int srsran_ue_ul_pregen_signals(srsran_ue_ul_t*, srsran_ue_ul_cfg_t*)
+{
+  fprintf(stderr, "[srsran_ue_ul] pregenerated signals are not provided: every subframe generates its DMRS\n");
+  return SRSRAN_ERROR;
+}
+
+int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* entries, void* stream)
+{
+  if (nof_ue == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!entries) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  hipStream_t                  st = (hipStream_t)stream;
+  std::vector<srsran_ue_ul_t*> objs;            // the distinct cell objects, in order of first use
+  std::vector<uint32_t>        slot(nof_ue);    // the entry's index among its object's entries
+  std::vector<uint32_t>        count, samples;  // per object: entries, entries that want samples
+  std::vector<uint32_t>        obj_of(nof_ue);
+  for (uint32_t i = 0; i < nof_ue; i++) {
+    const srsran_ue_ul_gpu_entry_t& e = entries[i];
+    if (!e.q || !e.q->gpu || !e.sf || !e.cfg || !((UeUlGpu*)e.q->gpu)->hop_ok) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (!e.cfg->grant_available) {
+      fprintf(stderr, "[srsran_ue_ul] a batch entry without a PUSCH grant (PUCCH / SRS are not provided)\n");
+      return SRSRAN_ERROR;
+    }
+    if (srs_in_subframe(e.cfg, e.sf->tti)) {
+      return SRSRAN_ERROR;
+    }
+    size_t o = std::find(objs.begin(), objs.end(), e.q) - objs.begin();
+    if (o == objs.size()) {
+      objs.push_back(e.q);
+      count.push_back(0);
+      samples.push_back(0);
+    }
+    obj_of[i] = (uint32_t)o;
+    slot[i]   = count[o]++;
+    samples[o] += e.d_out ? 1 : 0;
+  }
+  for (size_t o = 0; o < objs.size(); o++) {
+    srsran_ue_ul_t* q = objs[o];
+    UeUlGpu*        g = (UeUlGpu*)q->gpu;
+    const size_t sf_re = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
+    if (!grow((void**)&g->d_grid, &g->grid_cap, count[o] * sf_re * sizeof(float2)) ||
+        !grow((void**)&g->d_samp, &g->samp_cap, (size_t)count[o] * q->fft.sf_sz * sizeof(float2))) {
+      return SRSRAN_ERROR;
+    }
+  }
+  std::vector<TxReq> r(nof_ue);
+  for (uint32_t i = 0; i < nof_ue; i++) {
+    const srsran_ue_ul_gpu_entry_t& e = entries[i];
+    srsran_ue_ul_t*                 q = e.q;
+    UeUlGpu*                        g = (UeUlGpu*)q->gpu;
+    const size_t sf_re = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
+    TxReq&       t     = r[i];
+    memset(&t, 0, sizeof(t));
+    t.pusch     = &q->pusch;
+    t.hop       = &g->hop;
+    t.dmrs_cfg  = &e.cfg->ul_cfg.dmrs;
+    t.sf        = e.sf;
+    t.cfg       = &e.cfg->ul_cfg.pusch;
+    t.uci       = e.uci;
+    t.d_data    = e.d_data;
+    t.d_grid    = g->d_grid + slot[i] * sf_re;
+    t.zero_rest = true;
+    if (e.d_out) {
+      t.samples_in  = g->d_samp + (size_t)slot[i] * q->fft.sf_sz;
+      t.samples_out = (float2*)e.d_out;
+      t.sf_len      = q->fft.sf_sz;
+      t.norm_mode   = e.cfg->normalize_mode == SRSRAN_UE_UL_NORMALIZE_MODE_FORCE_AMPLITUDE ? 1 : 0;
+      // ue_ul.c:345: the integer quotient nof_prb / 15 first
+      t.norm_factor = (float)(q->cell.nof_prb / 15) / sqrtf((float)e.cfg->ul_cfg.pusch.grant.L_prb) / 2;
+      t.force_peak  = e.cfg->force_peak_amplitude > 0 ? e.cfg->force_peak_amplitude : 1.0f;
+    }
+  }
+  std::vector<PuschTxUe> desc;
+  const PuschTxUe*       d_desc = nullptr;
+  const int              ret    = pusch_tx_run(&entries[0].q->pusch, nof_ue, r.data(), desc, &d_desc, st);
+  if (ret != SRSRAN_SUCCESS) {
+    return ret == SRSRAN_ERROR_INVALID_INPUTS ? ret : SRSRAN_ERROR;
+  }
+  for (size_t o = 0; o < objs.size(); o++) {
+    UeUlGpu* g = (UeUlGpu*)objs[o]->gpu;
+    if (samples[o] && srsran_ofdm_tx_gpu(&objs[o]->fft, (const cf_t*)g->d_grid, (cf_t*)g->d_samp, 1, count[o], 1.0f, st) !=
+                          SRSRAN_SUCCESS) {
+      return SRSRAN_ERROR;
+    }
+  }
+  for (uint32_t i = 0; i < nof_ue; i++) {
+    const srsran_ue_ul_gpu_entry_t& e = entries[i];
+    srsran_ue_ul_t*                 q = e.q;
+    UeUlGpu*                        g = (UeUlGpu*)q->gpu;
+    const size_t sf_re = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
+    if (e.d_grid &&
+        hipMemcpyAsync(e.d_grid, r[i].d_grid, sf_re * sizeof(float2), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      return SRSRAN_ERROR;
+    }
+    // apply_cfo (ue_ul.c:260-266): the samples times srsran_vec_apply_cfo's phasors of cfo_value / symbol_sz
+    const float f = e.cfg->cfo_value / (float)srsran_symbol_sz(q->cell.nof_prb);
+    if (e.d_out && e.cfg->cfo_en && f != 0.0f) {  // a zero frequency multiplies every sample by exactly 1
+      const uint32_t len = q->fft.sf_sz;
+      if (g->cfo_len != len || g->cfo_freq != f) {
+        float c, s;
+        cfo_phasor(f, &c, &s);
+        if (!grow((void**)&g->d_cfo, &g->cfo_cap, len * sizeof(float2)) ||
+            cfo_table_launch(c, s, g->d_cfo, len, st) != hipSuccess) {
+          return SRSRAN_ERROR;
+        }
+        g->cfo_len  = len;
+        g->cfo_freq = f;
+      }
+      float2* x = g->d_samp + (size_t)slot[i] * len;
+      if (cfo_launch(x, x, g->d_cfo, len, st) != hipSuccess) {
+        return SRSRAN_ERROR;
+      }
+    }
+    g->last_s     = desc[i].s_pack;
+    g->last_bits  = e.cfg->ul_cfg.pusch.grant.tb.nof_bits;
+    g->last_d     = desc[i].d;
+    g->last_re    = e.cfg->ul_cfg.pusch.grant.nof_re;
+    g->last_grid  = r[i].d_grid;
+    g->last_ngrid = (uint32_t)sf_re;
+  }
+  return pusch_tx_norm_launch(d_desc, nof_ue, st) == hipSuccess ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+}
+
+int srsran_ue_ul_gpu_last(srsran_ue_ul_t* q,
+                          const uint8_t** d_scrambled,
+                          uint32_t*       nof_bits,
+                          const cf_t**    d_symbols,
+                          uint32_t*       nof_re,
+                          const cf_t**    d_grid,
+                          uint32_t*       nof_grid)
+{
+  if (!q || !q->gpu || !d_scrambled || !nof_bits || !d_symbols || !nof_re || !d_grid || !nof_grid) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  UeUlGpu* g = (UeUlGpu*)q->gpu;
+  if (g->last_bits == 0) {
+    return SRSRAN_ERROR;
+  }
+  *d_scrambled = g->last_s;
+  *nof_bits    = g->last_bits;
+  *d_symbols   = (const cf_t*)g->last_d;
+  *nof_re      = g->last_re;
+  *d_grid      = (const cf_t*)g->last_grid;
+  *nof_grid    = g->last_ngrid;
+  return SRSRAN_SUCCESS;
+}
+
+// ue_ul.c:618-659
+int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_cfg_t* cfg, srsran_pusch_data_t* data)
+{
+  if (!q || !q->gpu || !sf || !cfg || !data) {
+    return SRSRAN_ERROR;
+  }
+  // DTX to NACK in channel-selection mode; all DTX: no HARQ-ACK
+  if (cfg->ul_cfg.pucch.ack_nack_feedback_mode != SRSRAN_PUCCH_ACK_NACK_FEEDBACK_MODE_NORMAL) {
+    const uint32_t nack      = srsran_uci_cfg_total_ack(&cfg->ul_cfg.pusch.uci_cfg);
+    uint32_t       dtx_count = 0;
+    for (uint32_t a = 0; a < nack && a < SRSRAN_UCI_MAX_ACK_BITS; a++) {
+      if (data->uci.ack.ack_value[a] == 2) {
+        data->uci.ack.ack_value[a] = 0;
+        dtx_count++;
+      }
+    }
+    if (dtx_count == nack) {
+      for (int i = 0; i < SRSRAN_MAX_CARRIERS; i++) {
+        cfg->ul_cfg.pusch.uci_cfg.ack[i].nof_acks = 0;
+      }
+    }
+  }
+  UeUlGpu*     g      = (UeUlGpu*)q->gpu;
+  const size_t sf_len = q->cell.nof_prb ? q->fft.sf_sz : 0;
+  if (!cfg->grant_available) {
+    const srsran_uci_cfg_t& pu = cfg->ul_cfg.pucch.uci_cfg;
+    if ((srsran_uci_cfg_total_ack(&pu) > 0 || pu.cqi.data_enable || pu.cqi.ri_len > 0 || data->uci.scheduling_request) &&
+        cfg->cc_idx == 0) {
+      fprintf(stderr, "[srsran_ue_ul] PUCCH transmission is not provided\n");
+      return SRSRAN_ERROR;
+    }
+    if (srs_in_subframe(cfg, sf->tti)) {
+      return SRSRAN_ERROR;
+    }
+    if (sf_len && q->out_buffer) {
+      memset(q->out_buffer, 0, sf_len * sizeof(cf_t));
+    }
+    return SRSRAN_SUCCESS;
+  }
+  if (!g->hop_ok || !q->out_buffer) {
+    return SRSRAN_ERROR;
+  }
+  hipStream_t    st     = sch_stream(&q->pusch.ul_sch);
+  const int      tbs    = cfg->ul_cfg.pusch.grant.tb.tbs;
+  const uint32_t nbytes = tbs > 0 ? (uint32_t)tbs / 8 : 0;
+  const size_t   o_out  = ((size_t)nbytes + 31) & ~(size_t)15;
+  if (nbytes && !data->ptr) {
+    fprintf(stderr, "[srsran_ue_ul] encoding from the soft buffer (data == NULL) is not provided\n");
+    return SRSRAN_ERROR;
+  }
+  if (!grow((void**)&g->d_io, &g->io_cap, o_out + sf_len * sizeof(cf_t)) ||
+      (nbytes && hipMemcpyAsync(g->d_io, data->ptr, nbytes, hipMemcpyHostToDevice, st) != hipSuccess)) {
+    return SRSRAN_ERROR;
+  }
+  srsran_ue_ul_gpu_entry_t e = {q, sf, cfg, &data->uci, nbytes ? g->d_io : nullptr, (cf_t*)(g->d_io + o_out), nullptr};
+  int                      ret = srsran_ue_ul_gpu_tx_batch(1, &e, st);
+  if (ret == SRSRAN_SUCCESS &&
+      hipMemcpyAsync(q->out_buffer, g->d_io + o_out, sf_len * sizeof(cf_t), hipMemcpyDeviceToHost, st) != hipSuccess) {
+    ret = SRSRAN_ERROR;
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    ret = SRSRAN_ERROR;
+  }
+  return ret == SRSRAN_SUCCESS ? 1 : SRSRAN_ERROR;
 }
 
 }  // extern "C"

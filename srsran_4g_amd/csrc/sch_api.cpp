@@ -29,6 +29,7 @@
 #include "uci_kernel.h"
 #include "pdsch_internal.h"
 #include "ulsch_batch.h"
+#include "pusch_tx_internal.h"
 #include "stage_copy.h"
 #include "stage_timing.h"
 
@@ -314,6 +315,8 @@ struct SchCtx {
   size_t      hubs_cap = 0;
   uint8_t*    d_enc = nullptr;     // DL-SCH encode: descriptors, TB CRCs, unpacked e bits, staging
   size_t      enc_cap = 0;
+  uint8_t*    d_ultx = nullptr;    // UL-SCH transmit: descriptors, UCI bit lists, e / g / q bits, symbols
+  size_t      ultx_cap = 0;
   short*      d_wide = nullptr;    // llr_is_8bit, K <= 800: the widened soft buffers the 16-bit decoders read
   size_t      wide_cap = 0;        // rows of kWideStride
 };
@@ -1185,6 +1188,7 @@ void srsran_sch_free(srsran_sch_t* q)
     hipFree(x->d_ubs);
     hipHostFree(x->h_ubs);
     hipFree(x->d_enc);
+    hipFree(x->d_ultx);
     hipFree(x->d_wide);
     delete x;
   }
@@ -2265,6 +2269,48 @@ void qpp_coeffs(uint32_t idx, uint32_t* f1, uint32_t* f2);
 }  // namespace srsran_amd
 extern "C" {
 
+// encode_tb_off's split of the E bits over the blocks (sch.c:271-305); the K2 blocks come first.  Appends the TB's
+// code block descriptors: c.e holds the byte offset e_off + (bits before the block) and c.tb_crc the TB index t, both
+// fixed up once the scratch is allocated.  *wp: the E bits used.
+typedef std::map<uint32_t, std::pair<const uint16_t*, uint32_t>> EncFwdMap;  // (cb_idx, rv) -> table, looked up once
+static int enc_push_cbs(std::vector<EncCb>& cb, EncFwdMap& fwd, const srsran_cbsegm_t& s, uint32_t Qm, uint32_t rv,
+                        uint32_t nof_e_bits, const uint8_t* d_data, uint32_t tbs, size_t e_off, uint32_t t, uint32_t* wp_out)
+{
+  const uint32_t Gp = nof_e_bits / Qm, gamma = Gp % s.C;
+  uint32_t       rp = 0, wp = 0;
+  for (uint32_t i = 0; i < s.C; i++) {
+    const uint32_t K   = i < s.C2 ? s.K2 : s.K1;
+    const uint32_t idx = i < s.C2 ? s.K2_idx : s.K1_idx;
+    EncCb          c;
+    memset(&c, 0, sizeof(c));
+    c.rlen = s.C > 1 ? K - 24 : K;
+    c.E    = i <= s.C - gamma - 1 ? Qm * (Gp / s.C) : Qm * ((Gp + s.C - 1) / s.C);
+    c.K    = K;
+    c.rp   = rp;
+    c.cb_crc   = s.C > 1;
+    c.tb_bytes = tbs / 8;
+    c.data     = d_data;
+    qpp_coeffs(idx, &c.f1, &c.f2);
+    auto it = fwd.find(idx * 4 + rv);
+    if (it == fwd.end()) {
+      std::pair<const uint16_t*, uint32_t> v;
+      if (!rm_fwd_table(idx, rv, &v.first, &v.second)) {
+        return SRSRAN_ERROR;
+      }
+      it = fwd.emplace(idx * 4 + rv, v).first;
+    }
+    c.fwd = it->second.first;
+    c.N   = it->second.second;
+    c.e    = (uint8_t*)(uintptr_t)(e_off + wp);  // offsets: fixed up after the allocation
+    c.tb_crc = (const uint32_t*)(uintptr_t)t;
+    cb.push_back(c);
+    rp += c.rlen;
+    wp += c.E;
+  }
+  *wp_out = wp;
+  return SRSRAN_SUCCESS;
+}
+
 int srsran_dlsch_gpu_encode_batch(srsran_sch_t* q, uint32_t nof_tb, const srsran_dlsch_gpu_enc_t* tbs, void* stream)
 {
   if (!q || !q->gpu || (nof_tb && !tbs)) {
@@ -2280,7 +2326,7 @@ int srsran_dlsch_gpu_encode_batch(srsran_sch_t* q, uint32_t nof_tb, const srsran
   std::vector<size_t>  e_off(nof_tb);
   size_t               e_tot = 0;
   uint32_t             max_bytes = 0;
-  std::map<uint32_t, std::pair<const uint16_t*, uint32_t>> fwd;  // (cb_idx, rv) -> table, looked up once
+  EncFwdMap            fwd;
   for (uint32_t t = 0; t < nof_tb; t++) {
     const srsran_dlsch_gpu_enc_t& in = tbs[t];
     srsran_cbsegm_t               s;
@@ -2294,37 +2340,10 @@ int srsran_dlsch_gpu_encode_batch(srsran_sch_t* q, uint32_t nof_tb, const srsran
     e_off[t] = e_tot;
     e_tot += (in.nof_e_bits + 15) & ~15u;
     max_bytes = std::max(max_bytes, (in.nof_e_bits + 7) / 8);
-    // encode_tb_off's split of the E bits over the blocks (sch.c:271-305); the K2 blocks come first
-    const uint32_t Gp = in.nof_e_bits / in.Qm, gamma = Gp % s.C;
-    uint32_t       rp = 0, wp = 0;
-    for (uint32_t i = 0; i < s.C; i++) {
-      const uint32_t K   = i < s.C2 ? s.K2 : s.K1;
-      const uint32_t idx = i < s.C2 ? s.K2_idx : s.K1_idx;
-      EncCb          c;
-      memset(&c, 0, sizeof(c));
-      c.rlen = s.C > 1 ? K - 24 : K;
-      c.E    = i <= s.C - gamma - 1 ? in.Qm * (Gp / s.C) : in.Qm * ((Gp + s.C - 1) / s.C);
-      c.K    = K;
-      c.rp   = rp;
-      c.cb_crc   = s.C > 1;
-      c.tb_bytes = in.tbs / 8;
-      c.data     = in.d_data;
-      qpp_coeffs(idx, &c.f1, &c.f2);
-      auto it = fwd.find(idx * 4 + in.rv);
-      if (it == fwd.end()) {
-        std::pair<const uint16_t*, uint32_t> v;
-        if (!rm_fwd_table(idx, in.rv, &v.first, &v.second)) {
-          return SRSRAN_ERROR;
-        }
-        it = fwd.emplace(idx * 4 + in.rv, v).first;
-      }
-      c.fwd = it->second.first;
-      c.N   = it->second.second;
-      c.e    = (uint8_t*)(uintptr_t)(e_off[t] + wp);  // offsets: fixed up after the allocation
-      c.tb_crc = (const uint32_t*)(uintptr_t)t;
-      cb.push_back(c);
-      rp += c.rlen;
-      wp += c.E;
+    uint32_t wp = 0;
+    const int r = enc_push_cbs(cb, fwd, s, in.Qm, in.rv, in.nof_e_bits, in.d_data, in.tbs, e_off[t], t, &wp);
+    if (r != SRSRAN_SUCCESS) {
+      return r;
     }
     if (wp > in.nof_e_bits) {
       return SRSRAN_ERROR_INVALID_INPUTS;
@@ -2403,6 +2422,402 @@ int srsran_dlsch_encode2(srsran_sch_t*       q,
 int srsran_dlsch_encode(srsran_sch_t* q, srsran_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits)
 {
   return srsran_dlsch_encode2(q, cfg, data, e_bits, 0, 1);
+}
+
+}  // extern "C"
+
+// ---------------- UL-SCH transmit with UCI (sch.c:1195-1337; uci.c:200-257, 334-361, 457-632) ----------------
+namespace {
+
+// (32, O) basis sequences, 36.212 Table 5.2.2.6.4-1, as block_dev.h's kBlockBasis (a __constant__ the host cannot
+// read): bit n of word i is M_{i,n}
+const uint16_t kBlockBasisHost[32] = {0x403, 0x607, 0x749, 0x50D, 0x48F, 0x5D3, 0x755, 0x599, 0x69B, 0x65D, 0x6E5,
+                                      0x567, 0x7A9, 0x6AB, 0x4B1, 0x6F3, 0x277, 0x139, 0x0FB, 0x061, 0x445, 0x60B,
+                                      0x591, 0x717, 0x3DF, 0x4E3, 0x32D, 0x3AF, 0x175, 0x1FD, 0x7FF, 0x001};
+
+// srsran_block_encode (block.c:78-104): the codeword of the first 11 input bits, repeated up to nout bits
+void block_encode(const uint8_t* in, uint32_t nin, uint8_t* out, uint32_t nout)
+{
+  uint32_t w = 0;
+  for (uint32_t i = 0; i < std::min(nin, 11u); i++) {
+    w |= (uint32_t)(in[i] & 1u) << i;
+  }
+  for (uint32_t i = 0; i < nout; i++) {
+    out[i] = (uint8_t)(__builtin_popcount(w & kBlockBasisHost[i % 32]) & 1);
+  }
+}
+
+// encode_cqi_long (uci.c:225-257): CRC8 (0x19B), the tail-biting rate-1/3 code (0x6D, 0x4F, 0x57, K = 7;
+// convcoder.c:43-69) and srsran_rm_conv_tx (rm_conv.c:43-88) to Q bits
+bool cqi_encode_long(const uint8_t* data, uint32_t nbits, uint8_t* out, uint32_t Q)
+{
+  if (nbits + 8 >= 512) {  // SRSRAN_UCI_MAX_CQI_LEN_PUSCH
+    return false;
+  }
+  const uint32_t       F = nbits + 8;
+  std::vector<uint8_t> in(F), coded(3 * F);
+  uint32_t             crc = 0;
+  for (uint32_t i = 0; i < nbits; i++) {
+    in[i]              = data[i] & 1u;
+    const uint32_t top = ((crc >> 7) & 1u) ^ in[i];
+    crc                = ((crc << 1) & 0xFFu) ^ (top ? 0x9Bu : 0u);
+  }
+  for (uint32_t i = 0; i < 8; i++) {
+    in[nbits + i] = (uint8_t)((crc >> (7 - i)) & 1u);
+  }
+  static const uint32_t poly[3] = {0x6D, 0x4F, 0x57};
+  uint32_t              sr      = 0;
+  for (uint32_t i = F - 6; i < F; i++) {
+    sr = (sr << 1) | in[i];
+  }
+  for (uint32_t i = 0; i < F; i++) {
+    sr = (sr << 1) | in[i];
+    for (uint32_t j = 0; j < 3; j++) {
+      coded[3 * i + j] = (uint8_t)(__builtin_popcount(sr & poly[j]) & 1);
+    }
+  }
+  static const uint8_t perm[32] = {1, 17, 9,  25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
+                                   0, 16, 8,  24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};  // RM_PERM_CC
+  const uint32_t       nrows = (F - 1) / 32 + 1, Kp = nrows * 32, ndummy = Kp - F;
+  std::vector<uint8_t> tmp(3 * Kp);
+  uint32_t             k = 0;
+  for (uint32_t s = 0; s < 3; s++) {
+    for (uint32_t j = 0; j < 32; j++) {
+      for (uint32_t i = 0; i < nrows; i++) {
+        const uint32_t x = i * 32 + perm[j];
+        tmp[k++]         = x < ndummy ? kTxNull : coded[(x - ndummy) * 3 + s];
+      }
+    }
+  }
+  for (uint32_t n = 0, j = 0; n < Q; j = (j + 1) % (3 * Kp)) {
+    if (tmp[j] != kTxNull) {
+      out[n++] = tmp[j];
+    }
+  }
+  return true;
+}
+
+// encode_ri_ack / encode_ack_long and the repetition of srsran_uci_encode_ack_ri (uci.c:457-510, 600-613): the type
+// of every bit of the Q' symbols
+void ri_ack_types(const uint8_t* data, uint32_t O, uint32_t Qm, uint32_t Qp, std::vector<uint8_t>& t)
+{
+  t.assign((size_t)Qp * Qm, TX_BIT_0);
+  uint8_t  enc[32];
+  uint32_t len;
+  if (O == 1) {
+    len = Qm;
+    for (uint32_t i = 0; i < Qm; i++) {
+      enc[i] = i == 0 ? (data[0] ? TX_BIT_1 : TX_BIT_0) : i == 1 ? TX_BIT_REPETITION : TX_BIT_PLACEHOLDER;
+    }
+  } else if (O == 2) {
+    const uint8_t o[3] = {(uint8_t)(data[0] ? 1 : 0), (uint8_t)(data[1] ? 1 : 0), (uint8_t)((data[0] ^ data[1]) ? 1 : 0)};
+    len                = 3 * Qm;  // [o0 o1 x..] [o2 o0 x..] [o1 o2 x..]
+    for (uint32_t s = 0; s < 3; s++) {
+      for (uint32_t i = 0; i < Qm; i++) {
+        enc[s * Qm + i] = i < 2 ? o[(2 * s + i) % 3] : TX_BIT_PLACEHOLDER;
+      }
+    }
+  } else {
+    len = 32;
+    block_encode(data, O, enc, 32);
+  }
+  for (size_t i = 0; i < t.size(); i++) {
+    t[i] = enc[i % len];
+  }
+}
+
+// uci_ack_scramble_tdd (uci.c:548-579)
+void ack_scramble_tdd(std::vector<uint8_t>& q, uint32_t O_ack, uint32_t N_bundle)
+{
+  if (N_bundle == 0 || q.empty()) {
+    return;
+  }
+  static const uint8_t w_scram[4][4] = {{1, 1, 1, 1}, {1, 0, 1, 0}, {1, 1, 0, 0}, {1, 0, 0, 1}};  // Table 5.2.2.6-A
+  const uint32_t       wi = (N_bundle - 1) % 4, m = O_ack == 1 ? 1 : 3;
+  uint8_t              q_m1 = q[0];
+  uint32_t             k = 0;
+  for (size_t i = 0; i < q.size(); i++) {
+    if (q[i] == TX_BIT_REPETITION) {
+      if (i > 0) {
+        q[i] = (uint8_t)(((q_m1 == TX_BIT_1 ? 1 : 0) + w_scram[wi][k / m]) % 2);
+      }
+      k = (k + 1) % (4 * m);
+    } else if (q[i] != TX_BIT_PLACEHOLDER) {
+      q_m1 = q[i];
+      q[i] = (uint8_t)(((q[i] == TX_BIT_1 ? 1 : 0) + w_scram[wi][k / m]) % 2);
+      k    = (k + 1) % (4 * m);
+    }
+  }
+}
+
+struct UlsTxPlan {
+  srsran_cbsegm_t      s;
+  uint32_t             Qm, nsymb, H, rows, ri_Qp, ack_Qp, cqi_Qp, G;
+  std::vector<uint8_t> cqi, ri, ack;
+};
+
+// srsran_ulsch_encode's host part: returns (Q'_ACK + Q'_RI) Qm or an error
+int ulsch_tx_plan(srsran_pusch_cfg_t* cfg, const srsran_uci_value_t* uci, UlsTxPlan* p)
+{
+  const uint32_t nb_q = cfg->grant.tb.nof_bits;
+  p->Qm               = srsran_mod_bits_x_symbol(cfg->grant.tb.mod);
+  p->nsymb            = cfg->grant.nof_symb;
+  if (p->Qm == 0 || p->nsymb == 0) {
+    fprintf(stderr, "[srsran_sch] Invalid input\n");
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  // the multiplexing kernel's shapes: QPSK / 16QAM / 64QAM, whole interleaver columns, four symbols a thread
+  if (p->Qm > 6 || p->nsymb > 14 || nb_q % p->Qm || (nb_q / p->Qm) % p->nsymb ||
+      (nb_q / p->Qm) % PUSCH_TX_SYM_PER_THREAD || cfg->grant.tb.rv < 0 || cfg->grant.tb.rv > 3) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  srsran_cbsegm_t& s = p->s;
+  if (cfg->grant.tb.tbs < 0 || srsran_cbsegm(&s, (uint32_t)cfg->grant.tb.tbs)) {
+    fprintf(stderr, "[srsran_sch] Error computing segmentation for TBS=%d\n", cfg->grant.tb.tbs);
+    return SRSRAN_ERROR;
+  }
+  if (s.F) {
+    fprintf(stderr, "[srsran_sch] Error filler bits are not supported. Use standard TBS\n");
+    return SRSRAN_ERROR;
+  }
+  cfg->K_segm = s.C1 * s.K1 + s.C2 * s.K2;
+  p->H        = nb_q / p->Qm;
+  p->rows     = p->H / p->nsymb;
+  p->ri_Qp = p->ack_Qp = p->cqi_Qp = 0;
+
+  srsran_cqi_cfg_t& cq = cfg->uci_cfg.cqi;
+  uint8_t           cqi_buff[SRSRAN_CQI_MAX_BITS];
+  memset(cqi_buff, 0, sizeof(cqi_buff));
+  int cqi_len = 0;
+  if (cq.data_enable) {
+    if (!uci || (cqi_len = srsran_cqi_value_pack(&cq, const_cast<srsran_cqi_value_t*>(&uci->cqi), cqi_buff)) < 0 ||
+        cqi_len > (int)UCI_MAX_CQI_BITS) {
+      fprintf(stderr, "[srsran_sch] Error encoding CQI bits\n");
+      return SRSRAN_ERROR;
+    }
+  }
+  const uint32_t nack = srsran_uci_cfg_total_ack(&cfg->uci_cfg);
+  if ((nack > 0 || cq.ri_len > 0) && !uci) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (cq.ri_len > 0) {
+    if (cq.ri_len > 2) {  // the reference encodes ri[2] = {ri, 0}: one or two bits
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    float beta = beta_ri(cfg->uci_offset.I_offset_ri);
+    if (s.tbs == 0) {
+      beta /= beta_cqi(cfg->uci_offset.I_offset_cqi);
+    }
+    p->ri_Qp = qprime_ri_ack(cfg->K_segm, cfg->grant.L_prb, p->nsymb, cq.ri_len, (uint32_t)cqi_len, beta);
+    if ((int)p->ri_Qp < 0) {
+      return (int)p->ri_Qp;
+    }
+    const uint8_t ri[2] = {uci->ri, 0};
+    ri_ack_types(ri, cq.ri_len, p->Qm, p->ri_Qp, p->ri);
+  }
+  if (p->ri_Qp > 4 * p->rows || p->ri_Qp > p->H) {  // uci.c:400-415 "Error interleaving"
+    fprintf(stderr, "[srsran_sch] UCI does not fit the PUSCH interleaver (Q'_RI=%u rows=%u)\n", p->ri_Qp, p->rows);
+    return SRSRAN_ERROR;
+  }
+  if (cqi_len > 0) {
+    const float beta = beta_cqi(cfg->uci_offset.I_offset_cqi);
+    p->cqi_Qp        = qprime_cqi(cfg->K_segm, cfg->grant.L_prb, p->nsymb, (uint32_t)cqi_len, beta, p->ri_Qp);
+    if ((uint64_t)p->cqi_Qp + p->ri_Qp > p->H) {
+      return SRSRAN_ERROR;
+    }
+    p->cqi.assign((size_t)p->cqi_Qp * p->Qm, 0);
+    if (cqi_len <= 11) {
+      block_encode(cqi_buff, (uint32_t)cqi_len, p->cqi.data(), (uint32_t)p->cqi.size());
+    } else if (!cqi_encode_long(cqi_buff, (uint32_t)cqi_len, p->cqi.data(), (uint32_t)p->cqi.size())) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  p->G = p->H - p->ri_Qp - p->cqi_Qp;
+  if (nack > 0) {
+    if (nack > SRSRAN_UCI_MAX_ACK_BITS) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    float beta = beta_harq(cfg->uci_offset.I_offset_ack);
+    if (s.tbs == 0) {
+      beta /= beta_cqi(cfg->uci_offset.I_offset_cqi);
+    }
+    p->ack_Qp = qprime_ri_ack(cfg->K_segm, cfg->grant.L_prb, p->nsymb, nack, (uint32_t)cqi_len, beta);
+    if ((int)p->ack_Qp < 0) {
+      return (int)p->ack_Qp;
+    }
+    if (p->ack_Qp > 4 * p->rows) {  // uci.c:373-387
+      fprintf(stderr, "[srsran_sch] UCI does not fit the PUSCH interleaver (Q'_ACK=%u rows=%u)\n", p->ack_Qp, p->rows);
+      return SRSRAN_ERROR;
+    }
+    ri_ack_types(uci->ack.ack_value, nack, p->Qm, p->ack_Qp, p->ack);
+    ack_scramble_tdd(p->ack, nack, cfg->uci_cfg.ack[0].N_bundle);
+  }
+  return (int)((p->ack_Qp + p->ri_Qp) * p->Qm);
+}
+
+}  // namespace
+
+namespace srsran_amd {
+
+int ulsch_tx_prepare(srsran_sch_t* q, uint32_t n, UlschTxJob* jobs, PuschTxUe* desc, hipStream_t st)
+{
+  if (!q || !q->gpu || (n && (!jobs || !desc))) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  SchCtx*                x = (SchCtx*)q->gpu;
+  std::vector<UlsTxPlan> plan(n);
+  std::vector<EncTb>     tb;
+  std::vector<EncCb>     cb;
+  EncFwdMap              fwd;
+  std::vector<uint8_t>   lists;  // every job's CQI bits, RI types, ACK types
+  struct Off {
+    size_t cqi, ri, ack, e, g, qb, sb, d;
+    int    tb;
+  };
+  std::vector<Off> off(n);
+  size_t           e_tot = 0, bits_tot = 0, sym_tot = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    UlschTxJob& j = jobs[i];
+    UlsTxPlan&  p = plan[i];
+    j.ret         = j.cfg ? ulsch_tx_plan(j.cfg, j.uci, &p) : SRSRAN_ERROR_INVALID_INPUTS;
+    if (j.ret < 0) {
+      return j.ret;
+    }
+    Off& o = off[i];
+    o.cqi  = lists.size();
+    lists.insert(lists.end(), p.cqi.begin(), p.cqi.end());
+    o.ri = lists.size();
+    lists.insert(lists.end(), p.ri.begin(), p.ri.end());
+    o.ack = lists.size();
+    lists.insert(lists.end(), p.ack.begin(), p.ack.end());
+    o.tb = -1;
+    o.e  = e_tot;
+    if (p.s.tbs > 0) {
+      if (!j.d_data) {
+        fprintf(stderr, "[srsran_sch] encoding from the soft buffer (data == NULL) is not provided\n");
+        return j.ret = SRSRAN_ERROR;
+      }
+      const uint32_t ne = p.G * p.Qm;
+      uint32_t       wp = 0;
+      o.tb              = (int)tb.size();
+      const int r = enc_push_cbs(cb, fwd, p.s, p.Qm, (uint32_t)j.cfg->grant.tb.rv, ne, j.d_data, p.s.tbs, e_tot,
+                                 (uint32_t)o.tb, &wp);
+      if (r != SRSRAN_SUCCESS || wp > ne) {
+        return j.ret = r != SRSRAN_SUCCESS ? r : SRSRAN_ERROR_INVALID_INPUTS;
+      }
+      tb.push_back({j.d_data, nullptr, nullptr, nullptr, p.s.tbs / 8, ne});
+      e_tot += align16(ne);
+    }
+    const size_t nbytes = align16((size_t)p.H * p.Qm / 8);
+    o.g  = bits_tot;
+    o.qb = bits_tot + nbytes;
+    o.sb = bits_tot + 2 * nbytes;
+    bits_tot += 3 * nbytes;
+    o.d = sym_tot;
+    sym_tot += p.H;
+  }
+  // device scratch: [EncTb][EncCb][lists] (uploaded) [TB CRCs][e bits][g / q / scrambled bits][symbols]
+  const size_t o_cb = align16(tb.size() * sizeof(EncTb)), o_lists = o_cb + align16(cb.size() * sizeof(EncCb));
+  const size_t o_crc = o_lists + align16(lists.size()), o_e = o_crc + align16(tb.size() * sizeof(uint32_t));
+  const size_t o_bits = o_e + e_tot, o_sym = o_bits + bits_tot, need = o_sym + sym_tot * sizeof(float2);
+  if (!grow_dev((void**)&x->d_ultx, &x->ultx_cap, need)) {
+    return SRSRAN_ERROR;
+  }
+  uint8_t*  base  = x->d_ultx;
+  uint32_t* d_crc = (uint32_t*)(base + o_crc);
+  for (size_t t = 0; t < tb.size(); t++) {
+    tb[t].crc = d_crc + t;
+  }
+  for (EncCb& c : cb) {
+    c.e      = base + o_e + (size_t)(uintptr_t)c.e;
+    c.tb_crc = d_crc + (size_t)(uintptr_t)c.tb_crc;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const UlsTxPlan& p = plan[i];
+    const Off&       o = off[i];
+    PuschTxUe&       u = desc[i];
+    u.cqi    = base + o_lists + o.cqi;
+    u.ri     = base + o_lists + o.ri;
+    u.ack    = base + o_lists + o.ack;
+    u.e      = o.tb >= 0 ? base + o_e + o.e : nullptr;
+    u.g_pack = jobs[i].want_g ? base + o_bits + o.g : nullptr;
+    u.q_pack = jobs[i].want_q ? base + o_bits + o.qb : nullptr;
+    u.s_pack = base + o_bits + o.sb;
+    u.d      = (float2*)(base + o_sym) + o.d;
+    u.mod    = (uint32_t)jobs[i].cfg->grant.tb.mod;
+    u.Qm     = p.Qm;
+    u.rows   = p.rows;
+    u.cols   = p.nsymb;
+    u.H      = p.H;
+    u.ncqi   = p.cqi_Qp * p.Qm;
+    u.ne     = o.tb >= 0 ? p.G * p.Qm : 0;
+    u.ri_Qp  = p.ri_Qp;
+    u.ack_Qp = p.ack_Qp;
+    static const uint8_t kRiNorm[4] = {1, 4, 7, 10}, kRiExt[4] = {0, 3, 5, 8};    // uci.c:397-398
+    static const uint8_t kAckNorm[4] = {2, 3, 8, 9}, kAckExt[4] = {1, 2, 6, 7};  // uci.c:370-371
+    memcpy(u.ri_col, p.nsymb > 10 ? kRiNorm : kRiExt, 4);
+    memcpy(u.ack_col, p.nsymb > 10 ? kAckNorm : kAckExt, 4);
+  }
+  if ((!tb.empty() && hipMemcpyAsync(base, tb.data(), tb.size() * sizeof(EncTb), hipMemcpyHostToDevice, st) != hipSuccess) ||
+      (!cb.empty() &&
+       hipMemcpyAsync(base + o_cb, cb.data(), cb.size() * sizeof(EncCb), hipMemcpyHostToDevice, st) != hipSuccess) ||
+      (!lists.empty() &&
+       hipMemcpyAsync(base + o_lists, lists.data(), lists.size(), hipMemcpyHostToDevice, st) != hipSuccess) ||
+      enc_tb_crc_launch((const EncTb*)base, (uint32_t)tb.size(), st) != hipSuccess ||
+      enc_cb_launch((const EncCb*)(base + o_cb), (uint32_t)cb.size(), st) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+}  // namespace srsran_amd
+
+extern "C" {
+
+int srsran_ulsch_encode(srsran_sch_t*       q,
+                        srsran_pusch_cfg_t* cfg,
+                        uint8_t*            data,
+                        srsran_uci_value_t* uci_data,
+                        uint8_t*            g_bits,
+                        uint8_t*            q_bits)
+{
+  if (!q || !q->gpu || !cfg || !g_bits || !q_bits) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  SchCtx*        x      = (SchCtx*)q->gpu;
+  const uint32_t nbytes = cfg->grant.tb.tbs > 0 ? (uint32_t)cfg->grant.tb.tbs / 8 : 0;
+  if (nbytes && !data) {
+    fprintf(stderr, "[srsran_sch] encoding from the soft buffer (data == NULL) is not provided\n");
+    return SRSRAN_ERROR;
+  }
+  // payload and the descriptor on the device for the length of the call
+  uint8_t* d_io = nullptr;
+  if (hipMallocAsync((void**)&d_io, align16(nbytes + 16) + sizeof(PuschTxUe), x->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  PuschTxUe* d_desc = (PuschTxUe*)(d_io + align16(nbytes + 16));
+  PuschTxUe  u;
+  memset(&u, 0, sizeof(u));
+  UlschTxJob job = {cfg, uci_data, nbytes ? d_io : nullptr, true, true, 0};
+  int        ret = SRSRAN_ERROR;
+  if (!nbytes || hipMemcpyAsync(d_io, data, nbytes, hipMemcpyHostToDevice, x->stream) == hipSuccess) {
+    ret = ulsch_tx_prepare(q, 1, &job, &u, x->stream);
+    if (ret == SRSRAN_SUCCESS) {
+      const uint32_t ng = (u.ncqi + u.ne + 7) / 8, nq = u.H * u.Qm / 8;
+      ret               = job.ret;
+      if (hipMemcpyAsync(d_desc, &u, sizeof(u), hipMemcpyHostToDevice, x->stream) != hipSuccess ||
+          pusch_tx_mux_launch(d_desc, 1, u.H, x->stream) != hipSuccess ||
+          (ng && hipMemcpyAsync(g_bits, u.g_pack, ng, hipMemcpyDeviceToHost, x->stream) != hipSuccess) ||
+          hipMemcpyAsync(q_bits, u.q_pack, nq, hipMemcpyDeviceToHost, x->stream) != hipSuccess) {
+        ret = SRSRAN_ERROR;
+      }
+    }
+  }
+  hipFreeAsync(d_io, x->stream);
+  if (hipStreamSynchronize(x->stream) != hipSuccess) {
+    ret = SRSRAN_ERROR;
+  }
+  return ret;
 }
 
 }  // extern "C"

@@ -1,15 +1,17 @@
 /*
- * include/srsran_pucch.h -- MI355X PUCCH receive (eNB side): formats 1/1a/1b/2/2a/2b/3, as a C-ABI
- * drop-in with the reference's names, argument meaning, return codes and write-backs.
+ * include/srsran_pucch.h -- MI355X PUCCH receive (eNB side) and transmit (UE side): formats
+ * 1/1a/1b/2/2a/2b/3, as a C-ABI drop-in with the reference's names, argument meaning, return codes
+ * and write-backs.
  *
  * Replaces:
  *   srsran_pucch_format_t, srsran_pucch_cfg_t          lib/include/srsran/phy/phch/pucch_cfg.h:29-88
  *   srsran_ack_nack_feedback_mode_t                    lib/include/srsran/phy/common/phy_common.h:313-318
- *   srsran_pucch_t, srsran_pucch_res_t, srsran_pucch_init_enb / free / set_cell / decode and the
- *   resource helpers                                   lib/include/srsran/phy/phch/pucch.h:42-184
+ *   srsran_pucch_t, srsran_pucch_res_t, srsran_pucch_init_enb / init_ue / free / set_cell / decode /
+ *   encode and the resource helpers                    lib/include/srsran/phy/phch/pucch.h:42-184
  *   srsran_pucch_proc_select_format / get_resources / get_npucch, srsran_pucch_cs_get_ack
  *                                                      lib/include/srsran/phy/phch/pucch_proc.h
- *   srsran_refsignal_dmrs_N_rs / dmrs_pucch_symbol     lib/include/srsran/phy/ch_estimation/refsignal_ul.h
+ *   srsran_refsignal_dmrs_N_rs / dmrs_pucch_symbol / dmrs_pucch_gen / dmrs_pucch_put (the last two in
+ *   a _cell form: there is no srsran_refsignal_ul_t)   lib/include/srsran/phy/ch_estimation/refsignal_ul.h
  *   srsran_chest_ul_estimate_pucch                     lib/include/srsran/phy/ch_estimation/chest_ul.h:127-131
  *
  * Buffers of the reference's calls are host memory (subframe grids of nof_prb * 12 * 2 * N_symb(cp)
@@ -17,7 +19,10 @@
  * squares with the 2a / 2b DMRS hypotheses, EPRE / RSRP / TA / noise, the equaliser, DMRS detection
  * and the per-format decoders.  srsran_pucch_gpu_get_batch (added) does what srsran_enb_ul_get_pucch
  * does (enb_ul.c:156-273) for many UEs of one or more cells in one launch, from device grids.
- * Not provided: the UE side (srsran_pucch_encode), the Cedron TA estimator, SRS.
+ * The UE side (csrc/pucch_tx_kernel.hip) forms every RE of a transmission on the GPU from the coded
+ * bits: modulation, sequences, covers, the format 3 spreading and DFT, the DMRS; srsran_ue_ul_encode
+ * and srsran_ue_ul_gpu_tx_batch (srsran_ue_ul.h) run it for whole subframes.
+ * Not provided: the Cedron TA estimator, SRS.
  */
 #ifndef SRSRAN_AMD_PUCCH_H
 #define SRSRAN_AMD_PUCCH_H
@@ -203,6 +208,23 @@ int srsran_pucch_decode(srsran_pucch_t*        q,
                         srsran_chest_ul_res_t* channel,
                         cf_t*                  sf_symbols,
                         srsran_pucch_res_t*    data);
+
+/* ---- transmit, UE side (pucch.c:83, 768-794; refsignal_ul.c:432-552) ---- */
+int srsran_pucch_init_ue(srsran_pucch_t* q);
+/* Host grid in and out: only the data REs of cfg->format / cfg->n_pucch are written, the rest of sf_symbols is
+ * left as it is.  Writes cfg->pucch2_drs_bits for 2a / 2b.  SRSRAN_ERROR for a PRB outside the cell or an
+ * unsupported format, SRSRAN_ERROR_INVALID_INPUTS for NULL. */
+int srsran_pucch_encode(srsran_pucch_t*     q,
+                        srsran_ul_sf_cfg_t* sf,
+                        srsran_pucch_cfg_t* cfg,
+                        srsran_uci_value_t* uci_data,
+                        cf_t*               sf_symbols);
+/* r_pucch: 2 * N_rs * 12 values, [(slot * N_rs + m) * 12 + n]; d(10) of 2a / 2b from cfg->pucch2_drs_bits */
+int srsran_refsignal_dmrs_pucch_gen_cell(const srsran_cell_t* cell,
+                                         srsran_ul_sf_cfg_t*  sf,
+                                         srsran_pucch_cfg_t*  cfg,
+                                         cf_t*                r_pucch);
+int srsran_refsignal_dmrs_pucch_put_cell(const srsran_cell_t* cell, srsran_pucch_cfg_t* cfg, cf_t* r_pucch, cf_t* output);
 
 /* ---- added: srsran_enb_ul_get_pucch for many UEs in one launch ----
  * Per entry: the cell's chest object (cell, smoothing filter), the subframe, the PUCCH configuration

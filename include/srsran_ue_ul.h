@@ -1,23 +1,31 @@
 /*
- * include/srsran_ue_ul.h -- MI355X UE uplink transmit (PUSCH branch) as a C-ABI drop-in.
+ * include/srsran_ue_ul.h -- MI355X UE uplink transmit (PUSCH and PUCCH branches) as a C-ABI drop-in.
  *
  * Replaces, with the reference's names, argument meaning and return codes:
  *   srsran_ue_ul_powerctrl_t, srsran_ul_cfg_t, srsran_ue_ul_normalize_mode_t, srsran_ue_ul_cfg_t
  *                                            lib/include/srsran/phy/ue/ue_ul.h:49-92
  *   srsran_refsignal_srs_cfg_t               lib/include/srsran/phy/ch_estimation/refsignal_ul.h:53-70
  *   srsran_pusch_hopping_cfg_t               lib/include/srsran/phy/phch/pusch_cfg.h:35-42
- *   srsran_ue_ul_t, srsran_ue_ul_init / free / set_cell / encode
+ *   srsran_ue_ul_t, srsran_ue_ul_init / free / set_cell / encode, srsran_ue_ul_pucch_resource_selection,
+ *   srsran_ue_ul_sr_send_tti, srsran_ue_ul_gen_sr
  *                                            lib/include/srsran/phy/ue/ue_ul.h:94-142, lib/src/phy/ue/ue_ul.c:41-175, 246-351,
- *                                            618-659
+ *                                            497-659
+ *   srsran_uci_data_t                        lib/include/srsran/phy/phch/uci_cfg.h:61-64
+ *   srsran_refsignal_srs_pucch_shortened (as _cfg, without the unused object)
+ *                                            lib/src/phy/ch_estimation/refsignal_ul.c:625-642
  * with srsran_pusch_init_ue / srsran_pusch_encode / srsran_refsignal_dmrs_pusch_put_cell (srsran_pusch.h) and
  * srsran_ulsch_encode (srsran_sch.h) underneath.
  *
  * srsran_ue_ul_encode with a grant: the grid zeroed, srsran_pusch_encode, the DMRS put, SC-FDMA modulation
  * (freq_shift_f = 0.5, normalize = true, the cell's CP), apply_cfo, apply_norm -- all on the GPU
  * (csrc/pusch_tx_kernel.hip, csrc/ofdm_kernel.hip); q->out_buffer (host) receives the subframe's samples.
+ * Without a grant and with UCI pending (or a scheduling request) on cc_idx 0: the PUCCH branch (ue_ul.c:510-558) --
+ * format and resource selection on a copy of the UCI value (cfg->ul_cfg.pucch.format / n_pucch are written, data->uci
+ * is not), sf->shortened by the shortened rule, then the grid zeroed, srsran_pucch_encode and the PUCCH DMRS in one
+ * kernel (csrc/pucch_tx_kernel.hip), the same modulator, apply_cfo and apply_norm from (float)nof_prb / 15 / 10.
  * srsran_ue_ul_gpu_tx_batch (added) does the same for many UEs of one or more cells on device buffers.
  *
- * Not provided (SRSRAN_ERROR with a message): the PUCCH and SRS-only branches of srsran_ue_ul_encode, an SRS
+ * Not provided (SRSRAN_ERROR with a message): the SRS-only branch of srsran_ue_ul_encode, an SRS
  * configured for transmission in the subframe (srs_tx_enabled, ue_ul.c:453-462; every other subframe is encoded),
  * srsran_ue_ul_pregen_signals, srsran_ue_ul_set_cfr, a grant whose L_prb is not 2^a 3^b 5^c, filler bits.  srsran_ue_ul_dci_to_pusch_grant, srsran_ue_ul_pusch_hopping and the power
  * helpers are not declared: the caller supplies the grant with n_prb_tilde set, as for the receive side.
@@ -125,6 +133,27 @@ int srsran_ue_ul_pregen_signals(srsran_ue_ul_t* q, srsran_ue_ul_cfg_t* cfg);
  * error.  data->ptr: the host payload. */
 int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_cfg_t* cfg, srsran_pusch_data_t* data);
 
+/* ---- host helpers of the PUCCH branch, value-exact (ue_ul.c:497-506, 561-614; refsignal_ul.c:625-642) ---- */
+typedef struct {
+  srsran_uci_cfg_t   cfg;
+  srsran_uci_value_t value;
+} srsran_uci_data_t;
+
+/* writes cfg->format and cfg->n_pucch; b: b(0) b(1) of format 1b with channel selection */
+void srsran_ue_ul_pucch_resource_selection(const srsran_cell_t*      cell,
+                                           srsran_pucch_cfg_t*       cfg,
+                                           const srsran_uci_cfg_t*   uci_cfg,
+                                           const srsran_uci_value_t* uci_value,
+                                           uint8_t                   b[SRSRAN_UCI_MAX_ACK_BITS]);
+/* 1 when current_tti is an SR opportunity of cfg->I_sr (36.213 Table 10.1.5-1), 0 when not or when no SR is
+ * configured, -1 for I_sr > 157 */
+int  srsran_ue_ul_sr_send_tti(const srsran_pucch_cfg_t* cfg, uint32_t current_tti);
+bool srsran_ue_ul_gen_sr(srsran_ue_ul_cfg_t* cfg, srsran_ul_sf_cfg_t* sf, srsran_uci_data_t* uci_data, bool sr_request);
+/* writes sf->shortened: format 1x in a cell SRS subframe with srs_cfg->configured and simul_ack */
+void srsran_refsignal_srs_pucch_shortened_cfg(srsran_ul_sf_cfg_t*         sf,
+                                              srsran_refsignal_srs_cfg_t* srs_cfg,
+                                              srsran_pucch_cfg_t*         pucch_cfg);
+
 /* ---- added: many UE subframes of one or more cells, asynchronous on `stream` ----
  * Every stage (TB CRC, code blocks, multiplexing + scrambling + mapping, transform precoding + DMRS, normalisation)
  * is one launch over all entries; the OFDM modulation is one launch pair per cell object, the CFO product one launch
@@ -132,7 +161,11 @@ int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_
  * The transmit scratch of entries[0].q serves the whole batch, and every object keeps device state between calls (its
  * grids, samples and the CFO phasor table): use one stream per object, one batch at a time, in stream order.  The
  * descriptors are uploaded from pageable host memory, so the call returns once they are staged, not before.
- * Entries must have grant_available; cfg->ul_cfg.pusch is updated as srsran_pusch_encode updates it. */
+ * cfg->ul_cfg.pusch is updated as srsran_pusch_encode updates it.
+ * An entry without grant_available is a PUCCH entry under srsran_ue_ul_encode's conditions (uci == NULL: an all-zero
+ * value; d_data is ignored): all of them go through one PUCCH launch and share the modulator and normalisation
+ * launches with the PUSCH entries; cfg->ul_cfg.pucch.format / n_pucch / pucch2_drs_bits and sf->shortened are written.
+ * An entry with nothing to send gets zeroed d_out / d_grid and is not an error. */
 typedef struct {
   srsran_ue_ul_t*           q;      /* the entry's cell (srsran_ue_ul_set_cell done) */
   srsran_ul_sf_cfg_t*       sf;
@@ -146,7 +179,8 @@ typedef struct {
 int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* entries, void* stream);
 
 /* added, read-only: device pointers to the last encode on this object (the last batch entry naming it): the packed
- * scrambled bits (nof_bits / 8 bytes), the modulation symbols (nof_re) and the subframe grid (nof_grid REs).
+ * scrambled bits (nof_bits / 8 bytes), the modulation symbols (nof_re) and the subframe grid (nof_grid REs); after a
+ * PUCCH subframe the grid alone, with nof_bits = nof_re = 0.
  * Valid until the next encode on the object or on the object whose scratch served the batch; SRSRAN_ERROR before
  * the first. */
 int srsran_ue_ul_gpu_last(srsran_ue_ul_t* q,

@@ -2,7 +2,8 @@
 // the resource helpers of pucch.c:943-1264, pucch_proc.c and refsignal_ul.c:360-429 restated on the
 // host, srsran_chest_ul_estimate_pucch (chest_ul.c:462-610), srsran_pucch_decode (pucch.c:797-872)
 // and srsran_pucch_gpu_get_batch (the sequence of enb_ul.c:156-273 for many UEs), over the kernel
-// of pucch_kernel.hip.
+// of pucch_kernel.hip; and the transmit side of the UE (pucch.c:583-623, 768-794, refsignal_ul.c:432-552):
+// srsran_pucch_init_ue, srsran_pucch_encode and the DMRS generation / mapping over pucch_tx_kernel.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -16,6 +17,7 @@
 
 #include "../../include/srsran_pucch.h"
 #include "pucch_kernel.h"
+#include "pucch_tx_kernel.h"
 
 namespace srsran_amd {
 hipStream_t chest_ul_stream(srsran_chest_ul_t* q);
@@ -392,7 +394,8 @@ struct PucchGpu {
   PucchCand*    d_cand = nullptr;
   PucchCandOut* d_out  = nullptr;
   uint32_t      cap    = 0;        // candidates
-  float2*       d_re   = nullptr;  // srsran_pucch_decode: gathered data REs and estimates
+  float2*       d_re   = nullptr;  // srsran_pucch_decode: gathered data REs and estimates; srsran_pucch_encode: z
+  PucchTxUe*    d_tx   = nullptr;  // srsran_pucch_encode: the descriptor (allocated by the first call)
 };
 
 bool reserve(PucchGpu* g, uint32_t n)
@@ -922,6 +925,7 @@ void srsran_pucch_free(srsran_pucch_t* q)
     hipFree(g->d_cand);
     hipFree(g->d_out);
     hipFree(g->d_re);
+    hipFree(g->d_tx);
     delete g;
   }
   memset(q, 0, sizeof(*q));
@@ -1148,6 +1152,262 @@ int srsran_pucch_gpu_get_batch(srsran_pucch_t*              q,
       } else {
         cfg->uci_cfg.is_scheduling_request_tti = true;
       }
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
+}  // extern "C"
+
+// ---------------- transmit (UE side) ----------------
+namespace {
+
+// (20, A) basis sequences, 36.212 Table 5.2.3.3-1: bit n of word i is M_{i,n}
+const uint16_t kPucchBasis[SRSRAN_UCI_CQI_CODED_PUCCH_B] = {0x0C03, 0x0E07, 0x1F49, 0x1D0D, 0x1C8F, 0x1DD3, 0x1F55,
+                                                            0x1D99, 0x1E9B, 0x1E5D, 0x1EE5, 0x1D67, 0x1FA9, 0x1EAB,
+                                                            0x14B1, 0x16F3, 0x1A77, 0x1939, 0x00FB, 0x0061};
+// (32, O) basis sequences, 36.212 Table 5.2.2.6.4-1 (as sch_api.cpp's kBlockBasisHost)
+const uint16_t kBlockBasis[32] = {0x403, 0x607, 0x749, 0x50D, 0x48F, 0x5D3, 0x755, 0x599, 0x69B, 0x65D, 0x6E5,
+                                  0x567, 0x7A9, 0x6AB, 0x4B1, 0x6F3, 0x277, 0x139, 0x0FB, 0x061, 0x445, 0x60B,
+                                  0x591, 0x717, 0x3DF, 0x4E3, 0x32D, 0x3AF, 0x175, 0x1FD, 0x7FF, 0x001};
+
+// srsran_uci_encode_cqi_pucch (uci.c:92-106): bit i of the result is b(i)
+uint64_t encode_cqi_pucch(const uint8_t* data, uint32_t len)
+{
+  uint32_t w = 0;
+  for (uint32_t n = 0; n < len && n < SRSRAN_UCI_MAX_CQI_LEN_PUCCH; n++) {
+    w |= (uint32_t)(data[n] & 1u) << n;
+  }
+  uint64_t b = 0;
+  for (uint32_t i = 0; i < SRSRAN_UCI_CQI_CODED_PUCCH_B; i++) {
+    b |= (uint64_t)(__builtin_popcount(w & kPucchBasis[i]) & 1) << i;
+  }
+  return b;
+}
+
+// encode_bits (pucch.c:583-623): the bits the kernel modulates, bit i of *bits is b(i); writes pucch2_drs_bits
+int tx_encode_bits(srsran_pucch_cfg_t* cfg, const srsran_uci_value_t* v, uint64_t* bits)
+{
+  const srsran_pucch_format_t f       = cfg->format;
+  const uint32_t              nof_ack = std::min<uint32_t>(srsran_uci_cfg_total_ack(&cfg->uci_cfg), SRSRAN_UCI_MAX_ACK_BITS);
+  *bits                               = 0;
+  if (is_f1(f)) {
+    for (uint32_t a = 0; a < nof_ack && a < 2; a++) {
+      *bits |= (uint64_t)(v->ack.ack_value[a] ? 1u : 0u) << a;  // any non-zero value modulates as 1
+    }
+  } else if (is_f2(f)) {
+    if (cfg->uci_cfg.cqi.ri_len) {  // RI goes alone
+      const uint8_t temp[2] = {v->ri, 0};
+      if (cfg->uci_cfg.cqi.ri_len > SRSRAN_UCI_MAX_CQI_LEN_PUCCH) {
+        return SRSRAN_ERROR;
+      }
+      *bits = encode_cqi_pucch(temp, std::min<uint32_t>(cfg->uci_cfg.cqi.ri_len, 2));
+    } else {
+      uint8_t   buff[SRSRAN_CQI_MAX_BITS] = {};
+      const int len = srsran_cqi_value_pack(&cfg->uci_cfg.cqi, const_cast<srsran_cqi_value_t*>(&v->cqi), buff);
+      if (len < 0 || len > SRSRAN_UCI_MAX_CQI_LEN_PUCCH) {
+        fprintf(stderr, "[srsran_pucch] Error encoding CQI\n");
+        return SRSRAN_ERROR;
+      }
+      *bits = encode_cqi_pucch(buff, (uint32_t)len);
+    }
+    if (f != SRSRAN_PUCCH_FORMAT_2) {
+      cfg->pucch2_drs_bits[0] = v->ack.ack_value[0];
+      cfg->pucch2_drs_bits[1] = v->ack.ack_value[1];  // ignored in format 2a
+    }
+  } else if (f == SRSRAN_PUCCH_FORMAT_3) {
+    uint32_t w = 0, k = 0;
+    for (; k < nof_ack; k++) {
+      w |= (uint32_t)(v->ack.ack_value[k] == 1 ? 1u : 0u) << k;
+    }
+    if (cfg->uci_cfg.is_scheduling_request_tti) {
+      w |= (uint32_t)(v->scheduling_request ? 1u : 0u) << k;
+      k++;
+    }
+    w &= 0x7FFu;  // srsran_block_encode takes the first 11 bits
+    for (uint32_t i = 0; i < SRSRAN_PUCCH3_NOF_BITS; i++) {
+      *bits |= (uint64_t)(__builtin_popcount(w & kBlockBasis[i % 32]) & 1) << i;
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// the cover arguments as the reference's tables hold them (pucch.c:211-217, refsignal_ul.c:46-53), from the phase in
+// units of pi / 12
+float cover_arg(uint8_t ph)
+{
+  switch (ph) {
+    case 8:
+      return (float)(2 * M_PI / 3);
+    case 12:
+      return (float)M_PI;
+    case 16:
+      return (float)(4 * M_PI / 3);
+    default:
+      return 0.0f;
+  }
+}
+
+// The transmit descriptor of (cell, subframe, cfg->format, cfg->n_pucch): build_cand's fields plus the cover
+// arguments, the bits and d(10).  Pointers are left null.
+int build_tx(const srsran_cell_t& cell, const srsran_ul_sf_cfg_t* sf, srsran_pucch_cfg_t* cfg, uint64_t bits, PucchTxUe& d)
+{
+  const CellTables& t = *cell_tables(cell);
+  PucchCand         c;
+  const int         err = build_cand(cell, t, nullptr, sf, cfg, c);
+  if (err != SRSRAN_SUCCESS) {
+    return err;
+  }
+  memset(&d, 0, sizeof(d));
+  d.ncell_re  = c.ncell_re;
+  d.nsym_slot = c.nsym_slot;
+  d.format    = c.format;
+  d.n_rs      = c.n_rs;
+  memcpy(d.phi, c.phi, sizeof(d.phi));
+  memcpy(d.rs_sym, c.rs_sym, sizeof(d.rs_sym));
+  memcpy(d.data_sym, c.data_sym, sizeof(d.data_sym));
+  memcpy(d.rs_ncs, c.rs_ncs, sizeof(d.rs_ncs));
+  memcpy(d.data_ncs, c.data_ncs, sizeof(d.data_ncs));
+  memcpy(d.f3_noc, c.f3_noc, sizeof(d.f3_noc));
+  for (uint32_t s = 0; s < 2; s++) {
+    const uint32_t ns = 2 * (sf->tti % 10) + s;
+    d.n_prb[s]        = c.n_prb[s];
+    d.n_sf[s]         = c.n_sf[s];
+    for (uint32_t m = 0; m < c.n_rs; m++) {
+      d.rs_warg[s][m] = cover_arg(c.rs_ph[s][m]);
+    }
+    for (uint32_t i = 0; i < c.n_sf[s] && is_f1(cfg->format); i++) {
+      // pucch.c:419-432: w_n_oc(i) of the DMRS n_oc, plus S(ns), both single precision
+      uint32_t n_oc = 0, n_prime = 0;
+      ncs_format1(t.n_cs_cell, cfg, cell.cp, true, ns, c.data_sym[i], &n_oc, &n_prime);
+      d.data_warg[s][i] = cover_arg(kDataW[c.n_sf[s] == 3 ? 1 : 0][n_oc % 3][i]) + (n_prime % 2 ? (float)(M_PI / 2) : 0.0f);
+    }
+  }
+  d.bits   = bits;
+  d.scr    = c.scr;
+  d.drs[0] = cfg->pucch2_drs_bits[0] ? 1 : 0;
+  d.drs[1] = cfg->pucch2_drs_bits[1] ? 1 : 0;
+  return SRSRAN_SUCCESS;
+}
+
+}  // namespace
+
+namespace srsran_amd {
+
+// srsran_pucch_encode up to the kernel, for the UE uplink (pusch_api.cpp): the descriptor of cfg->format /
+// cfg->n_pucch carrying *uci, pointers left null.  Writes cfg->pucch2_drs_bits for 2a / 2b.
+int pucch_tx_prepare(const srsran_cell_t&      cell,
+                     const srsran_ul_sf_cfg_t* sf,
+                     srsran_pucch_cfg_t*       cfg,
+                     const srsran_uci_value_t* uci,
+                     PucchTxUe*                d)
+{
+  uint64_t bits = 0;
+  if (tx_encode_bits(cfg, uci, &bits) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR;
+  }
+  return build_tx(cell, sf, cfg, bits, *d) == SRSRAN_SUCCESS ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+}
+
+}  // namespace srsran_amd
+
+extern "C" {
+
+// pucch.c:83
+int srsran_pucch_init_ue(srsran_pucch_t* q)
+{
+  const int ret = srsran_pucch_init_enb(q);
+  if (ret == SRSRAN_SUCCESS) {
+    q->is_ue = true;
+  }
+  return ret;
+}
+
+// pucch.c:768-794
+int srsran_pucch_encode(srsran_pucch_t*     q,
+                        srsran_ul_sf_cfg_t* sf,
+                        srsran_pucch_cfg_t* cfg,
+                        srsran_uci_value_t* uci_data,
+                        cf_t*               sf_symbols)
+{
+  if (!q || !q->gpu || !sf || !cfg || !uci_data || !sf_symbols || !cell_valid(q->cell)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  PucchGpu* g = (PucchGpu*)q->gpu;
+  PucchTxUe d;
+  if (pucch_tx_prepare(q->cell, sf, cfg, uci_data, &d) != SRSRAN_SUCCESS) {
+    fprintf(stderr, "[srsran_pucch] Error encoding PUCCH (format %s)\n", srsran_pucch_format_text(cfg->format));
+    return SRSRAN_ERROR;
+  }
+  if (!g->d_tx && hipMalloc((void**)&g->d_tx, sizeof(PucchTxUe)) != hipSuccess) {
+    g->d_tx = nullptr;
+    return SRSRAN_ERROR;
+  }
+  const uint32_t nre = (d.n_sf[0] + d.n_sf[1]) * SRSRAN_NRE;
+  cf_t           z[PUCCH_MAX_RE];
+  d.z_out = g->d_re;
+  if (hipMemcpyAsync(g->d_tx, &d, sizeof(d), hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+      pucch_tx_launch(g->d_tx, 1, g->stream) != hipSuccess ||
+      hipMemcpyAsync(z, g->d_re, nre * sizeof(float2), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+      hipStreamSynchronize(g->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  // pucch_put (pucch.c:321-367): only the data REs are written
+  for (uint32_t s = 0; s < 2; s++) {
+    for (uint32_t i = 0; i < d.n_sf[s]; i++) {
+      memcpy(&sf_symbols[(size_t)(s * d.nsym_slot + d.data_sym[i]) * d.ncell_re + d.n_prb[s] * SRSRAN_NRE],
+             &z[(s * d.n_sf[0] + i) * SRSRAN_NRE], SRSRAN_NRE * sizeof(cf_t));
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// refsignal_ul.c:432-512, r_pucch[(slot N_rs + m) 12 + n].  There is no device object to run on here: the values
+// are those of the kernel's per-RE function, evaluated on the host.
+int srsran_refsignal_dmrs_pucch_gen_cell(const srsran_cell_t* cell,
+                                         srsran_ul_sf_cfg_t*  sf,
+                                         srsran_pucch_cfg_t*  cfg,
+                                         cf_t*                r_pucch)
+{
+  if (!cell || !sf || !cfg || !r_pucch || !cell_valid(*cell)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  PucchTxUe d;
+  if (build_tx(*cell, sf, cfg, 0, d) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t s = 0; s < 2; s++) {
+    for (uint32_t m = 0; m < d.n_rs; m++) {
+      for (uint32_t n = 0; n < SRSRAN_NRE; n++) {
+        const float2 v = pucch_tx_re(d, s, true, m, n);
+        cf_t*        o = &r_pucch[(s * d.n_rs + m) * SRSRAN_NRE + n];
+        memcpy(o, &v, sizeof(v));
+      }
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// refsignal_ul.c:514-552
+int srsran_refsignal_dmrs_pucch_put_cell(const srsran_cell_t* cell, srsran_pucch_cfg_t* cfg, cf_t* r_pucch, cf_t* output)
+{
+  if (!cell || !cfg || !r_pucch || !output || !cell_valid(*cell)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  const uint32_t N_rs = srsran_refsignal_dmrs_N_rs(cfg->format, cell->cp), nsym = nsymb_slot(cell->cp);
+  if (!N_rs || cfg->delta_pucch_shift == 0) {
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t s = 0; s < 2; s++) {
+    const uint32_t n_prb = srsran_pucch_n_prb(cell, cfg, s);
+    if (n_prb >= cell->nof_prb) {
+      fprintf(stderr, "[srsran_refsignal] Invalid PUCCH n_prb=%u\n", n_prb);
+      return SRSRAN_ERROR;
+    }
+    for (uint32_t i = 0; i < N_rs; i++) {
+      const uint32_t l = srsran_refsignal_dmrs_pucch_symbol(i, cfg->format, cell->cp);
+      memcpy(&output[(size_t)(l + s * nsym) * cell->nof_prb * SRSRAN_NRE + n_prb * SRSRAN_NRE],
+             &r_pucch[(s * N_rs + i) * SRSRAN_NRE], SRSRAN_NRE * sizeof(cf_t));
     }
   }
   return SRSRAN_SUCCESS;

@@ -1,5 +1,6 @@
 // srsran_4g_amd/csrc/pusch_api.cpp -- C-ABI of the PUSCH receive path (include/srsran_pusch.h) and, at the end, of
-// the UE's PUSCH transmit path (srsran_pusch_encode, include/srsran_ue_ul.h):
+// the UE's uplink transmit path (srsran_pusch_encode, include/srsran_ue_ul.h: the PUSCH branch and, over
+// pucch_tx_kernel.hip, the PUCCH branch of srsran_ue_ul_encode / srsran_ue_ul_gpu_tx_batch):
 // PUSCH DMRS generation (refsignal_ul.c:95-358 restated), the UL channel estimator object
 // (chest_ul.c:53-433) and srsran_pusch_t (pusch.c:108-471), over the kernels of pusch_kernel.hip,
 // llr_kernel.hip and the UL-SCH decoder of sch_api.cpp.
@@ -17,10 +18,14 @@
 #include "llr_kernel.h"
 #include "ofdm_kernel.h"
 #include "pusch_kernel.h"
+#include "pucch_tx_kernel.h"
 #include "pusch_tx_internal.h"
 #include "ulsch_batch.h"
 
 namespace srsran_amd {
+// pucch_api.cpp: srsran_pucch_encode up to the kernel
+int pucch_tx_prepare(const srsran_cell_t& cell, const srsran_ul_sf_cfg_t* sf, srsran_pucch_cfg_t* cfg,
+                     const srsran_uci_value_t* uci, PucchTxUe* d);
 int         ulsch_decode_dev(srsran_sch_t* q, srsran_pusch_cfg_t* cfg, int16_t* d_q, const uint8_t* d_c, uint8_t* data,
                              srsran_uci_value_t* uci_data);
 hipStream_t sch_stream(srsran_sch_t* q);
@@ -1040,9 +1045,10 @@ struct TxReq {
 
 // srsran_pusch_encode for n transmissions up to the grids: checks, the UL-SCH step, then one multiplexing launch and
 // one transform-precoding launch over the batch.  desc / *d_desc: the descriptors (host copy, device array in
-// owner's scratch) for the caller's later stages.  Nothing is launched when a transmission is refused.
+// owner's scratch) for the caller's later stages.  Nothing is launched when a transmission is refused.  extra:
+// descriptors of the batch's other transmissions (PUCCH), appended after the n of PUSCH for the normalisation launch.
 int pusch_tx_run(srsran_pusch_t* owner, uint32_t n, const TxReq* r, std::vector<PuschTxUe>& desc,
-                 const PuschTxUe** d_desc, hipStream_t st)
+                 const PuschTxUe** d_desc, hipStream_t st, const std::vector<PuschTxUe>& extra = {})
 {
   PuschGpu* g = (PuschGpu*)owner->gpu;
   desc.assign(n, PuschTxUe{});
@@ -1113,11 +1119,12 @@ int pusch_tx_run(srsran_pusch_t* owner, uint32_t n, const TxReq* r, std::vector<
     jobs[i] = {cfg, r[i].uci, r[i].d_data, false, false, 0};
     max_H   = std::max(max_H, cfg->grant.nof_re);
   }
-  if (ulsch_tx_prepare(&owner->ul_sch, n, jobs.data(), desc.data(), st) != SRSRAN_SUCCESS) {
+  if (n && ulsch_tx_prepare(&owner->ul_sch, n, jobs.data(), desc.data(), st) != SRSRAN_SUCCESS) {
     fprintf(stderr, "[srsran_pusch] Error encoding TB\n");
     return SRSRAN_ERROR;
   }
-  const size_t o_dmrs = (n * sizeof(PuschTxUe) + 15) & ~(size_t)15;
+  desc.insert(desc.end(), extra.begin(), extra.end());
+  const size_t o_dmrs = (desc.size() * sizeof(PuschTxUe) + 15) & ~(size_t)15;
   if (!grow((void**)&g->d_tx, &g->tx_cap, o_dmrs + dmrs.size() * sizeof(cf_t))) {
     return SRSRAN_ERROR;
   }
@@ -1125,7 +1132,7 @@ int pusch_tx_run(srsran_pusch_t* owner, uint32_t n, const TxReq* r, std::vector<
     desc[i].dmrs = (const float2*)(g->d_tx + o_dmrs) + dmrs_off[i];
   }
   *d_desc = (const PuschTxUe*)g->d_tx;
-  if (hipMemcpyAsync(g->d_tx, desc.data(), n * sizeof(PuschTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
+  if (hipMemcpyAsync(g->d_tx, desc.data(), desc.size() * sizeof(PuschTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
       (!dmrs.empty() && hipMemcpyAsync(g->d_tx + o_dmrs, dmrs.data(), dmrs.size() * sizeof(cf_t), hipMemcpyHostToDevice,
                                        st) != hipSuccess) ||
       pusch_tx_mux_launch(*d_desc, n, max_H, st) != hipSuccess || pusch_tx_grid_launch(*d_desc, n, st) != hipSuccess) {
@@ -1148,11 +1155,14 @@ struct UeUlGpu {
   uint32_t  cfo_len = 0;
   uint8_t*  d_io = nullptr;    // sync API: payload, then the output samples
   size_t    io_cap = 0;
+  uint8_t*  d_ptx = nullptr;   // the PUCCH descriptors of a batch this object's scratch serves
+  size_t    ptx_cap = 0;
   // srsran_ue_ul_gpu_last
   const uint8_t* last_s = nullptr;
   const float2*  last_d = nullptr;
   const float2*  last_grid = nullptr;
   uint32_t       last_bits = 0, last_re = 0, last_ngrid = 0;
+  bool           last_ok = false;  // an encode has run (a PUCCH subframe leaves last_bits = last_re = 0)
 };
 
 // srs_tx_enabled (ue_ul.c:453-462): the subframe carries this UE's SRS when it is a cell-specific SRS subframe
@@ -1321,6 +1331,7 @@ void srsran_ue_ul_free(srsran_ue_ul_t* q)
     hipFree(g->d_samp);
     hipFree(g->d_cfo);
     hipFree(g->d_io);
+    hipFree(g->d_ptx);
     delete g;
   }
   srsran_ofdm_tx_free(&q->fft);
@@ -1337,6 +1348,7 @@ int srsran_ue_ul_set_cell(srsran_ue_ul_t* q, srsran_cell_t cell)
     UeUlGpu* g = (UeUlGpu*)q->gpu;
     g->hop_ok  = false;
     g->last_bits = 0;
+    g->last_ok   = false;
     if (srsran_ofdm_rx_set_prb(&q->fft, cell.cp, cell.nof_prb)) {  // srsran_ofdm_tx_set_prb: the same object
       fprintf(stderr, "[srsran_ue_ul] Error resizing FFT\n");
       return SRSRAN_ERROR;
@@ -1363,6 +1375,59 @@ int srsran_ue_ul_pregen_signals(srsran_ue_ul_t*, srsran_ue_ul_cfg_t*)
   return SRSRAN_ERROR;
 }
 
+// ue_ul.c:497-506
+void srsran_ue_ul_pucch_resource_selection(const srsran_cell_t*      cell,
+                                           srsran_pucch_cfg_t*       cfg,
+                                           const srsran_uci_cfg_t*   uci_cfg,
+                                           const srsran_uci_value_t* uci_value,
+                                           uint8_t                   b[SRSRAN_UCI_MAX_ACK_BITS])
+{
+  cfg->format  = srsran_pucch_proc_select_format(cell, cfg, uci_cfg, uci_value);
+  cfg->n_pucch = (uint16_t)srsran_pucch_proc_get_npucch(cell, cfg, uci_cfg, uci_value, b);
+}
+
+// ue_ul.c:561-600, 36.213 Table 10.1.5-1
+int srsran_ue_ul_sr_send_tti(const srsran_pucch_cfg_t* cfg, uint32_t current_tti)
+{
+  if (!cfg->sr_configured) {
+    return SRSRAN_SUCCESS;
+  }
+  static const uint32_t first[8] = {0, 5, 15, 35, 75, 155, 157, 158}, period[7] = {5, 10, 20, 40, 80, 2, 1};
+  const uint32_t        I_sr     = cfg->I_sr;
+  if (I_sr >= first[7]) {
+    return SRSRAN_ERROR;
+  }
+  uint32_t k = 0;
+  while (I_sr >= first[k + 1]) {
+    k++;
+  }
+  const uint32_t offset = I_sr - first[k];
+  return current_tti >= offset && (current_tti - offset) % period[k] == 0 ? 1 : SRSRAN_SUCCESS;
+}
+
+// ue_ul.c:602-614
+bool srsran_ue_ul_gen_sr(srsran_ue_ul_cfg_t* cfg, srsran_ul_sf_cfg_t* sf, srsran_uci_data_t* uci_data, bool sr_request)
+{
+  uci_data->value.scheduling_request = false;
+  if (srsran_ue_ul_sr_send_tti(&cfg->ul_cfg.pucch, sf->tti)) {
+    if (sr_request) {
+      uci_data->value.scheduling_request = true;
+    }
+    uci_data->cfg.is_scheduling_request_tti = true;
+    return true;
+  }
+  return false;
+}
+
+// refsignal_ul.c:625-642: format 1x is shortened in the cell's SRS subframes when ACK and SRS may coincide
+void srsran_refsignal_srs_pucch_shortened_cfg(srsran_ul_sf_cfg_t*         sf,
+                                              srsran_refsignal_srs_cfg_t* srs_cfg,
+                                              srsran_pucch_cfg_t*         pucch_cfg)
+{
+  sf->shortened = srs_cfg->configured && pucch_cfg->format < SRSRAN_PUCCH_FORMAT_2 && srs_cfg->simul_ack &&
+                  srs_send_cs(srs_cfg->subframe_config, sf->tti % 10);
+}
+
 int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* entries, void* stream)
 {
   if (nof_ue == 0) {
@@ -1371,22 +1436,65 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
   if (!entries) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
+  enum { K_PUSCH, K_PUCCH, K_NONE };
   hipStream_t                  st = (hipStream_t)stream;
   std::vector<srsran_ue_ul_t*> objs;            // the distinct cell objects, in order of first use
-  std::vector<uint32_t>        slot(nof_ue);    // the entry's index among its object's entries
-  std::vector<uint32_t>        count, samples;  // per object: entries, entries that want samples
-  std::vector<uint32_t>        obj_of(nof_ue);
+  std::vector<uint32_t>        slot(nof_ue);    // the entry's index among its object's transmissions
+  std::vector<uint32_t>        count, samples;  // per object: transmissions, transmissions that want samples
+  std::vector<uint32_t>        obj_of(nof_ue), kind(nof_ue), idx(nof_ue);  // idx: among the entries of its kind
+  std::vector<PucchTxUe>       pdesc;
+  uint32_t                     npusch = 0;
   for (uint32_t i = 0; i < nof_ue; i++) {
     const srsran_ue_ul_gpu_entry_t& e = entries[i];
     if (!e.q || !e.q->gpu || !e.sf || !e.cfg || !((UeUlGpu*)e.q->gpu)->hop_ok) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
-    if (!e.cfg->grant_available) {
-      fprintf(stderr, "[srsran_ue_ul] a batch entry without a PUSCH grant (PUCCH / SRS are not provided)\n");
-      return SRSRAN_ERROR;
-    }
-    if (srs_in_subframe(e.cfg, e.sf->tti)) {
-      return SRSRAN_ERROR;
+    if (e.cfg->grant_available) {
+      kind[i] = K_PUSCH;
+      idx[i]  = npusch++;
+      if (srs_in_subframe(e.cfg, e.sf->tti)) {
+        return SRSRAN_ERROR;
+      }
+    } else {
+      // the PUCCH branch of ue_ul.c:642-648 and pucch_encode (510-541) up to the kernel
+      srsran_pucch_cfg_t*     pc = &e.cfg->ul_cfg.pucch;
+      const srsran_uci_cfg_t& pu = pc->uci_cfg;
+      srsran_uci_value_t      value;
+      if (e.uci) {
+        value = *e.uci;
+      } else {
+        memset(&value, 0, sizeof(value));
+      }
+      const bool pending = srsran_uci_cfg_total_ack(&pu) > 0 || pu.cqi.data_enable || pu.cqi.ri_len > 0;
+      kind[i]            = (pending || value.scheduling_request) && e.cfg->cc_idx == 0 ? K_PUCCH : K_NONE;
+      if (kind[i] == K_PUCCH) {
+        if (!pc->rnti) {
+          fprintf(stderr, "[srsran_ue_ul] Encoding PUCCH: rnti not set in ul_cfg\n");
+          return SRSRAN_ERROR;
+        }
+        if (!srsran_pucch_cfg_isvalid(pc, e.q->cell.nof_prb)) {
+          fprintf(stderr, "[srsran_ue_ul] Invalid PUCCH configuration\n");
+          return SRSRAN_ERROR;
+        }
+      }
+      if (srs_in_subframe(e.cfg, e.sf->tti)) {  // with PUCCH or alone
+        return SRSRAN_ERROR;
+      }
+      if (kind[i] == K_PUCCH) {
+        srsran_uci_value_t value2 = value;  // the value that is encoded: b(0) b(1) of the selection go here
+        srsran_ue_ul_pucch_resource_selection(&e.q->cell, pc, &pc->uci_cfg, &value, value2.ack.ack_value);
+        if (pc->format == SRSRAN_PUCCH_FORMAT_ERROR) {
+          return SRSRAN_ERROR;
+        }
+        srsran_refsignal_srs_pucch_shortened_cfg(e.sf, &e.cfg->ul_cfg.srs, pc);
+        PucchTxUe d;
+        if (pucch_tx_prepare(e.q->cell, e.sf, pc, &value2, &d) != SRSRAN_SUCCESS) {
+          fprintf(stderr, "[srsran_ue_ul] Error encoding PUCCH\n");
+          return SRSRAN_ERROR;
+        }
+        idx[i] = (uint32_t)pdesc.size();
+        pdesc.push_back(d);
+      }
     }
     size_t o = std::find(objs.begin(), objs.end(), e.q) - objs.begin();
     if (o == objs.size()) {
@@ -1395,8 +1503,10 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
       samples.push_back(0);
     }
     obj_of[i] = (uint32_t)o;
-    slot[i]   = count[o]++;
-    samples[o] += e.d_out ? 1 : 0;
+    if (kind[i] != K_NONE) {
+      slot[i] = count[o]++;
+      samples[o] += e.d_out ? 1 : 0;
+    }
   }
   for (size_t o = 0; o < objs.size(); o++) {
     srsran_ue_ul_t* q = objs[o];
@@ -1407,13 +1517,39 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
       return SRSRAN_ERROR;
     }
   }
-  std::vector<TxReq> r(nof_ue);
+  std::vector<TxReq>     r(npusch);
+  std::vector<PuschTxUe> pnorm(pdesc.size(), PuschTxUe{});  // the normalisation stage of the PUCCH entries
   for (uint32_t i = 0; i < nof_ue; i++) {
     const srsran_ue_ul_gpu_entry_t& e = entries[i];
     srsran_ue_ul_t*                 q = e.q;
     UeUlGpu*                        g = (UeUlGpu*)q->gpu;
     const size_t sf_re = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
-    TxReq&       t     = r[i];
+    if (kind[i] == K_NONE) {  // nothing to send: zero outputs
+      if ((e.d_out && hipMemsetAsync(e.d_out, 0, q->fft.sf_sz * sizeof(float2), st) != hipSuccess) ||
+          (e.d_grid && hipMemsetAsync(e.d_grid, 0, sf_re * sizeof(float2), st) != hipSuccess)) {
+        return SRSRAN_ERROR;
+      }
+      continue;
+    }
+    const float2* samples_in = g->d_samp + (size_t)slot[i] * q->fft.sf_sz;
+    const uint32_t norm_mode = e.cfg->normalize_mode == SRSRAN_UE_UL_NORMALIZE_MODE_FORCE_AMPLITUDE ? 1 : 0;
+    const float   force_peak = e.cfg->force_peak_amplitude > 0 ? e.cfg->force_peak_amplitude : 1.0f;
+    if (kind[i] == K_PUCCH) {
+      PucchTxUe& d = pdesc[idx[i]];
+      d.grid       = g->d_grid + slot[i] * sf_re;
+      d.zero_rest  = 1;
+      if (e.d_out) {
+        PuschTxUe& u  = pnorm[idx[i]];
+        u.samples_in  = samples_in;
+        u.samples_out = (float2*)e.d_out;
+        u.sf_len      = q->fft.sf_sz;
+        u.norm_mode   = norm_mode;
+        u.norm_factor = (float)q->cell.nof_prb / 15 / 10;  // ue_ul.c:548: a float quotient here
+        u.force_peak  = force_peak;
+      }
+      continue;
+    }
+    TxReq& t = r[idx[i]];
     memset(&t, 0, sizeof(t));
     t.pusch     = &q->pusch;
     t.hop       = &g->hop;
@@ -1425,20 +1561,31 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
     t.d_grid    = g->d_grid + slot[i] * sf_re;
     t.zero_rest = true;
     if (e.d_out) {
-      t.samples_in  = g->d_samp + (size_t)slot[i] * q->fft.sf_sz;
+      t.samples_in  = samples_in;
       t.samples_out = (float2*)e.d_out;
       t.sf_len      = q->fft.sf_sz;
-      t.norm_mode   = e.cfg->normalize_mode == SRSRAN_UE_UL_NORMALIZE_MODE_FORCE_AMPLITUDE ? 1 : 0;
+      t.norm_mode   = norm_mode;
       // ue_ul.c:345: the integer quotient nof_prb / 15 first
       t.norm_factor = (float)(q->cell.nof_prb / 15) / sqrtf((float)e.cfg->ul_cfg.pusch.grant.L_prb) / 2;
-      t.force_peak  = e.cfg->force_peak_amplitude > 0 ? e.cfg->force_peak_amplitude : 1.0f;
+      t.force_peak  = force_peak;
     }
+  }
+  if (npusch == 0 && pdesc.empty()) {
+    return SRSRAN_SUCCESS;
   }
   std::vector<PuschTxUe> desc;
   const PuschTxUe*       d_desc = nullptr;
-  const int              ret    = pusch_tx_run(&entries[0].q->pusch, nof_ue, r.data(), desc, &d_desc, st);
+  const int              ret    = pusch_tx_run(&entries[0].q->pusch, npusch, r.data(), desc, &d_desc, st, pnorm);
   if (ret != SRSRAN_SUCCESS) {
     return ret == SRSRAN_ERROR_INVALID_INPUTS ? ret : SRSRAN_ERROR;
+  }
+  if (!pdesc.empty()) {  // every PUCCH entry of every cell in one launch
+    UeUlGpu* g0 = (UeUlGpu*)entries[0].q->gpu;
+    if (!grow((void**)&g0->d_ptx, &g0->ptx_cap, pdesc.size() * sizeof(PucchTxUe)) ||
+        hipMemcpyAsync(g0->d_ptx, pdesc.data(), pdesc.size() * sizeof(PucchTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
+        pucch_tx_launch((const PucchTxUe*)g0->d_ptx, (uint32_t)pdesc.size(), st) != hipSuccess) {
+      return SRSRAN_ERROR;
+    }
   }
   for (size_t o = 0; o < objs.size(); o++) {
     UeUlGpu* g = (UeUlGpu*)objs[o]->gpu;
@@ -1452,8 +1599,11 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
     srsran_ue_ul_t*                 q = e.q;
     UeUlGpu*                        g = (UeUlGpu*)q->gpu;
     const size_t sf_re = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
-    if (e.d_grid &&
-        hipMemcpyAsync(e.d_grid, r[i].d_grid, sf_re * sizeof(float2), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    if (kind[i] == K_NONE) {
+      continue;
+    }
+    const float2* grid = g->d_grid + slot[i] * sf_re;
+    if (e.d_grid && hipMemcpyAsync(e.d_grid, grid, sf_re * sizeof(float2), hipMemcpyDeviceToDevice, st) != hipSuccess) {
       return SRSRAN_ERROR;
     }
     // apply_cfo (ue_ul.c:260-266): the samples times srsran_vec_apply_cfo's phasors of cfo_value / symbol_sz
@@ -1475,14 +1625,16 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
         return SRSRAN_ERROR;
       }
     }
-    g->last_s     = desc[i].s_pack;
-    g->last_bits  = e.cfg->ul_cfg.pusch.grant.tb.nof_bits;
-    g->last_d     = desc[i].d;
-    g->last_re    = e.cfg->ul_cfg.pusch.grant.nof_re;
-    g->last_grid  = r[i].d_grid;
-    g->last_ngrid = (uint32_t)sf_re;
+    const bool pusch = kind[i] == K_PUSCH;
+    g->last_s        = pusch ? desc[idx[i]].s_pack : nullptr;
+    g->last_bits     = pusch ? e.cfg->ul_cfg.pusch.grant.tb.nof_bits : 0;
+    g->last_d        = pusch ? desc[idx[i]].d : nullptr;
+    g->last_re       = pusch ? e.cfg->ul_cfg.pusch.grant.nof_re : 0;
+    g->last_grid     = grid;
+    g->last_ngrid    = (uint32_t)sf_re;
+    g->last_ok       = true;
   }
-  return pusch_tx_norm_launch(d_desc, nof_ue, st) == hipSuccess ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+  return pusch_tx_norm_launch(d_desc, (uint32_t)desc.size(), st) == hipSuccess ? SRSRAN_SUCCESS : SRSRAN_ERROR;
 }
 
 int srsran_ue_ul_gpu_last(srsran_ue_ul_t* q,
@@ -1497,7 +1649,7 @@ int srsran_ue_ul_gpu_last(srsran_ue_ul_t* q,
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   UeUlGpu* g = (UeUlGpu*)q->gpu;
-  if (g->last_bits == 0) {
+  if (!g->last_ok) {
     return SRSRAN_ERROR;
   }
   *d_scrambled = g->last_s;
@@ -1536,9 +1688,21 @@ int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_
   if (!cfg->grant_available) {
     const srsran_uci_cfg_t& pu = cfg->ul_cfg.pucch.uci_cfg;
     if ((srsran_uci_cfg_total_ack(&pu) > 0 || pu.cqi.data_enable || pu.cqi.ri_len > 0 || data->uci.scheduling_request) &&
-        cfg->cc_idx == 0) {
-      fprintf(stderr, "[srsran_ue_ul] PUCCH transmission is not provided\n");
-      return SRSRAN_ERROR;
+        cfg->cc_idx == 0) {  // PUCCH, over the PCell only (ue_ul.c:642-648): a batch of one
+      hipStream_t st = sch_stream(&q->pusch.ul_sch);
+      if (!g->hop_ok || !q->out_buffer || !grow((void**)&g->d_io, &g->io_cap, sf_len * sizeof(cf_t))) {
+        return SRSRAN_ERROR;
+      }
+      srsran_ue_ul_gpu_entry_t e   = {q, sf, cfg, &data->uci, nullptr, (cf_t*)g->d_io, nullptr};
+      int                      ret = srsran_ue_ul_gpu_tx_batch(1, &e, st);
+      if (ret == SRSRAN_SUCCESS &&
+          hipMemcpyAsync(q->out_buffer, g->d_io, sf_len * sizeof(cf_t), hipMemcpyDeviceToHost, st) != hipSuccess) {
+        ret = SRSRAN_ERROR;
+      }
+      if (hipStreamSynchronize(st) != hipSuccess) {
+        ret = SRSRAN_ERROR;
+      }
+      return ret == SRSRAN_SUCCESS ? 1 : SRSRAN_ERROR;
     }
     if (srs_in_subframe(cfg, sf->tti)) {
       return SRSRAN_ERROR;

@@ -89,6 +89,10 @@ def lib():
                                                 ctypes.POINTER(srsran_chest_ul_res_t)], ctypes.c_int),
             "srsran_pucch_decode": ([PU, SF, CFG, ctypes.POINTER(srsran_chest_ul_res_t), _cfp, RES], ctypes.c_int),
             "srsran_pucch_gpu_get_batch": ([PU, u32, ctypes.POINTER(srsran_pucch_gpu_ue_t), RES], ctypes.c_int),
+            "srsran_pucch_init_ue": ([PU], ctypes.c_int),
+            "srsran_pucch_encode": ([PU, SF, CFG, UVAL, _cfp], ctypes.c_int),
+            "srsran_refsignal_dmrs_pucch_gen_cell": ([CELL, SF, CFG, _cfp], ctypes.c_int),
+            "srsran_refsignal_dmrs_pucch_put_cell": ([CELL, CFG, _cfp, _cfp], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -151,6 +155,36 @@ class Pucch:
     def free(self):
         if self.q.gpu:
             lib().srsran_pucch_free(ctypes.byref(self.q))
+
+
+class PucchUe(Pucch):
+    """srsran_pucch_t initialised for the UE side (transmit); raises RuntimeError without a HIP device."""
+
+    def __init__(self, cell):
+        self.q = srsran_pucch_t()
+        self.cell = cell
+        L = lib()
+        if L.srsran_pucch_init_ue(ctypes.byref(self.q)) != 0:
+            raise RuntimeError("srsran_pucch_init_ue failed: no HIP device?")
+        if L.srsran_pucch_set_cell(ctypes.byref(self.q), cell) != 0:
+            self.free()
+            raise ValueError("srsran_pucch_set_cell: invalid cell")
+
+    def encode(self, sf, cfg, uci_value, grid):
+        """srsran_pucch_encode into the host grid (contiguous complex64 array, modified in place)"""
+        return lib().srsran_pucch_encode(ctypes.byref(self.q), ctypes.byref(sf), ctypes.byref(cfg),
+                                         ctypes.byref(uci_value), grid.ctypes.data)
+
+    def put_dmrs(self, sf, cfg, grid):
+        """srsran_refsignal_dmrs_pucch_gen_cell + _put_cell into the host grid; returns (ret, r_pucch)"""
+        r = np.zeros(2 * 3 * 12, np.complex64)
+        L = lib()
+        ret = L.srsran_refsignal_dmrs_pucch_gen_cell(ctypes.byref(self.cell), ctypes.byref(sf), ctypes.byref(cfg),
+                                                     r.ctypes.data)
+        if ret == 0:
+            ret = L.srsran_refsignal_dmrs_pucch_put_cell(ctypes.byref(self.cell), ctypes.byref(cfg), r.ctypes.data,
+                                                         grid.ctypes.data)
+        return ret, r
 
 
 def estimate(chest, sf, cfg, grid):

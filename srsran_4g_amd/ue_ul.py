@@ -5,7 +5,7 @@ import ctypes
 
 import numpy as np
 
-from .pucch import srsran_pucch_cfg_t
+from .pucch import srsran_pucch_cfg_t, srsran_uci_cfg_t
 from .pusch import (lib as _pusch_lib, srsran_pusch_t, srsran_refsignal_dmrs_pusch_cfg_t, srsran_ul_sf_cfg_t)
 from .sch import Sch, _memcpy_d2h, srsran_pusch_cfg_t, srsran_sch_t, srsran_uci_value_t
 from .ue_dl import srsran_cell_t, srsran_ofdm_t
@@ -54,6 +54,10 @@ class srsran_ue_ul_t(ctypes.Structure):
                 ("pusch", srsran_pusch_t), ("out_buffer", ctypes.c_void_p), ("gpu", ctypes.c_void_p)]
 
 
+class srsran_uci_data_t(ctypes.Structure):
+    _fields_ = [("cfg", srsran_uci_cfg_t), ("value", srsran_uci_value_t)]
+
+
 class srsran_ue_ul_gpu_entry_t(ctypes.Structure):
     _fields_ = [("q", ctypes.POINTER(srsran_ue_ul_t)), ("sf", ctypes.POINTER(srsran_ul_sf_cfg_t)),
                 ("cfg", ctypes.POINTER(srsran_ue_ul_cfg_t)), ("uci", ctypes.POINTER(srsran_uci_value_t)),
@@ -89,6 +93,14 @@ def lib():
             "srsran_ue_ul_gpu_tx_batch": ([u32, ctypes.POINTER(srsran_ue_ul_gpu_entry_t), P], ctypes.c_int),
             "srsran_ue_ul_gpu_last": ([Q, ctypes.POINTER(P), ctypes.POINTER(u32), ctypes.POINTER(P),
                                        ctypes.POINTER(u32), ctypes.POINTER(P), ctypes.POINTER(u32)], ctypes.c_int),
+            "srsran_ue_ul_pucch_resource_selection": ([ctypes.POINTER(srsran_cell_t), ctypes.POINTER(srsran_pucch_cfg_t),
+                                                       ctypes.POINTER(srsran_uci_cfg_t),
+                                                       ctypes.POINTER(srsran_uci_value_t),
+                                                       ctypes.POINTER(ctypes.c_uint8)], None),
+            "srsran_ue_ul_sr_send_tti": ([ctypes.POINTER(srsran_pucch_cfg_t), u32], ctypes.c_int),
+            "srsran_ue_ul_gen_sr": ([UCFG, SF, ctypes.POINTER(srsran_uci_data_t), _b], _b),
+            "srsran_refsignal_srs_pucch_shortened_cfg": ([SF, ctypes.POINTER(srsran_refsignal_srs_cfg_t),
+                                                          ctypes.POINTER(srsran_pucch_cfg_t)], None),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -184,11 +196,14 @@ class UeUl:
         if lib().srsran_ue_ul_gpu_last(ctypes.byref(self.q), ctypes.byref(ds), ctypes.byref(nb), ctypes.byref(dd),
                                        ctypes.byref(nr), ctypes.byref(dg), ctypes.byref(ng)):
             raise RuntimeError("srsran_ue_ul_gpu_last: no encode to read")
+        # after a PUCCH subframe nof_bits = nof_re = 0: the grid alone
         s = torch.empty(nb.value // 8, dtype=torch.uint8)
         d = torch.empty(2 * nr.value, dtype=torch.float32)
         g = torch.empty(2 * ng.value, dtype=torch.float32)
-        _memcpy_d2h(s, ds.value, nb.value // 8)
-        _memcpy_d2h(d, dd.value, 8 * nr.value)
+        if nb.value:
+            _memcpy_d2h(s, ds.value, nb.value // 8)
+        if nr.value:
+            _memcpy_d2h(d, dd.value, 8 * nr.value)
         _memcpy_d2h(g, dg.value, 8 * ng.value)
         return s.numpy(), d.numpy().view(np.complex64), g.numpy().view(np.complex64)
 

@@ -159,23 +159,6 @@ void sync_sequences(uint32_t cell_id, std::vector<float2>& out)
   }
 }
 
-// PBCH REs (pbch.c srsran_pbch_cp with put): slot 1, symbols 0..3, the 72 central subcarriers; symbols 0, 1
-// (and 3 with the extended CP) skip the CRS positions k mod 3 = cell_id mod 3 of any port count
-std::vector<uint32_t> pbch_res(const srsran_cell_t& cell)
-{
-  const uint32_t nre = 12 * cell.nof_prb, nsymb = SRSRAN_CP_NSYMB(cell.cp), k0 = nre / 2 - 36, v = cell.id % 3;
-  std::vector<uint32_t> t;
-  for (uint32_t l = 0; l < 4; l++) {
-    const bool crs = l < 2 || (l == 3 && cell.cp != SRSRAN_CP_NORM);
-    for (uint32_t r = 0; r < 72; r++) {
-      if (!crs || (k0 + r) % 3 != v) {
-        t.push_back((nsymb + l) * nre + k0 + r);
-      }
-    }
-  }
-  return t;
-}
-
 bool ctrl_init(EnbDlGpu* g, const srsran_cell_t& cell)
 {
   if (srsran_regs_init_opts(&g->regs, cell, 1, false) != SRSRAN_SUCCESS) {

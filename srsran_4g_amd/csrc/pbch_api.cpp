@@ -1,0 +1,658 @@
+// srsran_4g_amd/csrc/pbch_api.cpp -- PBCH receiver and the UE's MIB decoder (include/srsran_pbch.h; pbch.c, ue_mib.c).
+//
+// Host: the RE table of srsran_pbch_cp (shared with the eNB's transmitter), the cell's scrambling sequence
+// (srsran_sequence_pbch: 1920 / 1728 bits of the Gold sequence of c_init = cell id), validation, descriptors of a
+// batch's entries, MIB unpacking.  GPU (pbch_kernel.hip): everything between the grid and the MIB bits, and the
+// objects' history and counters.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/srsran_pbch.h"
+#include "pbch_kernel.h"
+#include "pdsch_internal.h"
+
+using namespace srsran_amd;
+
+namespace srsran_amd {
+
+// symbols 0, 1 (and 3 with the extended CP) skip the CRS positions k mod 3 = cell_id mod 3 of any port count; the
+// start, 6 nof_prb - 36, is not PRB-aligned for an odd nof_prb
+std::vector<uint32_t> pbch_res(const srsran_cell_t& cell)
+{
+  const uint32_t nre = 12 * cell.nof_prb, nsymb = SRSRAN_CP_NSYMB(cell.cp), k0 = nre / 2 - 36, v = cell.id % 3;
+  std::vector<uint32_t> t;
+  for (uint32_t l = 0; l < 4; l++) {
+    const bool crs = l < 2 || (l == 3 && cell.cp != SRSRAN_CP_NORM);
+    for (uint32_t r = 0; r < 72; r++) {
+      if (!crs || (k0 + r) % 3 != v) {
+        t.push_back((nsymb + l) * nre + k0 + r);
+      }
+    }
+  }
+  return t;
+}
+
+}  // namespace srsran_amd
+
+namespace {
+
+constexpr uint32_t kMaxNre  = 12 * SRSRAN_MAX_PRB;
+constexpr uint32_t kMaxBits = 2 * PBCH_MAX_SYM;
+constexpr uint32_t kSeqWords = 4 * kMaxBits / 32;
+
+struct PbchGpu {
+  hipStream_t stream  = nullptr;
+  uint32_t*   d_re    = nullptr;  // PBCH_MAX_SYM
+  uint32_t*   d_seq   = nullptr;  // kSeqWords
+  float*      d_hist  = nullptr;  // 4 x kMaxBits
+  float*      d_try   = nullptr;  // PBCH_NANT_HYP x kMaxBits
+  PbchHypOut* d_hyp   = nullptr;  // PBCH_HYP
+  PbchState*  d_state = nullptr;
+  bool        ready   = false;  // a cell is set
+  // host-synchronous calls: slot 1's first four symbols of the grid and of every port's estimate, noise, result
+  float2*  d_grid  = nullptr;  // 4 x kMaxNre
+  float2*  d_ce    = nullptr;  // 4 ports x 4 x kMaxNre
+  float*   d_noise = nullptr;
+  PbchOut* d_out   = nullptr;
+  // batches whose first entry is this object
+  PbchEntry*             d_entries = nullptr;
+  uint32_t               entries_cap = 0;
+  std::vector<PbchEntry> h_entries;
+  // srsran_ue_mib_gpu_decode_batch: the object's grid, estimates (rows of 12 nof_prb) and measurements
+  float2* d_mib_grid = nullptr;
+  float2* d_mib_ce   = nullptr;
+  float*  d_mib_res  = nullptr;
+  uint32_t* d_mib_sf = nullptr;  // the subframe index the batch estimator reads: 0
+};
+
+// srsran_sequence_LTE_pr (sequence.c, 36.211 7.2): len bits of the Gold sequence of c_init, packed
+void gold_bits(uint32_t c_init, uint32_t len, uint32_t* out)
+{
+  uint32_t x1 = 1, x2 = c_init & 0x7fffffffu;
+  for (uint32_t n = 0; n < 1600 + len; n++) {
+    if (n >= 1600 && ((x1 ^ x2) & 1u)) {
+      out[(n - 1600) >> 5] |= 1u << ((n - 1600) & 31);
+    }
+    const uint32_t f1 = ((x1 >> 3) ^ x1) & 1u;
+    const uint32_t f2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 1u;
+    x1                = (x1 >> 1) | (f1 << 30);
+    x2                = (x2 >> 1) | (f2 << 30);
+  }
+}
+
+void pbch_free_gpu(PbchGpu* g)
+{
+  if (!g) {
+    return;
+  }
+  hipDeviceSynchronize();  // a batch on the caller's stream may still use the buffers
+  if (g->stream) {
+    hipStreamDestroy(g->stream);
+  }
+  hipFree(g->d_re);
+  hipFree(g->d_seq);
+  hipFree(g->d_hist);
+  hipFree(g->d_try);
+  hipFree(g->d_hyp);
+  hipFree(g->d_state);
+  hipFree(g->d_grid);
+  hipFree(g->d_ce);
+  hipFree(g->d_noise);
+  hipFree(g->d_out);
+  hipFree(g->d_entries);
+  hipFree(g->d_mib_grid);
+  hipFree(g->d_mib_ce);
+  hipFree(g->d_mib_res);
+  hipFree(g->d_mib_sf);
+  delete g;
+}
+
+bool usable(const srsran_pbch_t* q) { return q && q->gpu && ((const PbchGpu*)q->gpu)->ready; }
+
+// the part of an entry that belongs to the object
+PbchEntry object_entry(const srsran_pbch_t* q, bool mib_rule)
+{
+  const PbchGpu* g = (const PbchGpu*)q->gpu;
+  PbchEntry      e{};
+  e.re    = g->d_re;
+  e.seq   = g->d_seq;
+  e.hist  = g->d_hist;
+  e.tr    = g->d_try;
+  e.hyp   = g->d_hyp;
+  e.state = g->d_state;
+  e.nsym  = q->nof_symbols;
+  if (q->search_all_ports) {
+    e.nof_nant = 3;
+    e.nant[0] = 1, e.nant[1] = 2, e.nant[2] = 4;
+  } else {
+    e.nof_nant = 1;
+    e.nant[0]  = q->cell.nof_ports;
+  }
+  e.mib_rule = mib_rule ? 1u : 0u;
+  return e;
+}
+
+// the three launches for entries already described in owner->h_entries
+int enqueue(PbchGpu* owner, PbchOut* d_out, hipStream_t st)
+{
+  const uint32_t n = (uint32_t)owner->h_entries.size();
+  if (n > owner->entries_cap) {
+    hipDeviceSynchronize();  // an earlier batch on another stream may still read the descriptors
+    hipFree(owner->d_entries);
+    owner->d_entries = nullptr, owner->entries_cap = 0;
+    if (hipMalloc((void**)&owner->d_entries, n * sizeof(PbchEntry)) != hipSuccess) {
+      return SRSRAN_ERROR;
+    }
+    owner->entries_cap = n;
+  }
+  // h_entries is pageable: the runtime stages such a copy before it returns, so the next batch may overwrite the
+  // vector at once (phich_api.cpp relies on the same); calls that were ever to overlap on the host would need
+  // pinned staging per call
+  if (hipMemcpyAsync(owner->d_entries, owner->h_entries.data(), n * sizeof(PbchEntry), hipMemcpyHostToDevice, st) !=
+          hipSuccess ||
+      pbch_llr_launch(owner->d_entries, n, st) != hipSuccess || pbch_hyp_launch(owner->d_entries, n, st) != hipSuccess ||
+      pbch_select_launch(owner->d_entries, n, d_out, st) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// waits for the device and refreshes the host mirror(s)
+int refresh(srsran_pbch_t* q, uint32_t* miss_cnt)
+{
+  PbchGpu*  g = (PbchGpu*)q->gpu;
+  PbchState s{};
+  if (hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(&s, g->d_state, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  q->frame_idx = s.frame_idx;
+  if (miss_cnt) {
+    *miss_cnt = s.miss_cnt;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int set_state(srsran_pbch_t* q, const uint32_t* frame_idx, const uint32_t* miss_cnt)
+{
+  PbchGpu* g = (PbchGpu*)q->gpu;
+  hipDeviceSynchronize();
+  if (frame_idx && hipMemcpy(&g->d_state->frame_idx, frame_idx, sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  if (miss_cnt && hipMemcpy(&g->d_state->miss_cnt, miss_cnt, sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+// srsran_pbch_decode on host buffers; with mib_rule also srsran_ue_mib_decode's counter rules, *miss_cnt refreshed
+int decode_sync(srsran_pbch_t* q, srsran_chest_dl_res_t* channel, cf_t* sf_symbols[SRSRAN_MAX_PORTS],
+                uint8_t* bch_payload, uint32_t* nof_tx_ports, int* sfn_offset, bool mib_rule, uint32_t* miss_cnt)
+{
+  if (!q || !sf_symbols) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (!usable(q) || !channel || !sf_symbols[0]) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  PbchGpu*       g    = (PbchGpu*)q->gpu;
+  const uint32_t nre  = 12 * q->cell.nof_prb, slot = SRSRAN_CP_NSYMB(q->cell.cp) * nre, rows = 4 * nre;
+  const uint32_t np   = q->cell.nof_ports;
+  for (uint32_t p = 0; p < np; p++) {
+    if (!channel->ce[p][0]) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+  }
+  // slot 1's symbols 0..3 of rx antenna 0 and of every port's estimate on it (pbch.c:456-461)
+  if (hipMemcpyAsync(g->d_grid, sf_symbols[0] + slot, rows * sizeof(float2), hipMemcpyHostToDevice, g->stream) !=
+          hipSuccess ||
+      hipMemcpyAsync(g->d_noise, &channel->noise_estimate, sizeof(float), hipMemcpyHostToDevice, g->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t p = 0; p < np; p++) {
+    if (hipMemcpyAsync(g->d_ce + (size_t)p * rows, channel->ce[p][0] + slot, rows * sizeof(float2), hipMemcpyHostToDevice,
+                       g->stream) != hipSuccess) {
+      return SRSRAN_ERROR;
+    }
+  }
+  PbchEntry e = object_entry(q, mib_rule);
+  e.grid      = g->d_grid;
+  e.ce        = g->d_ce;
+  e.noise     = g->d_noise;
+  e.re_off    = slot;
+  e.ce_row    = rows;
+  e.ce_port   = rows;
+  g->h_entries.assign(1, e);
+  PbchOut   o{};
+  PbchState s{};
+  if (enqueue(g, g->d_out, g->stream) != SRSRAN_SUCCESS ||
+      hipMemcpyAsync(&o, g->d_out, sizeof(o), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+      hipMemcpyAsync(&s, g->d_state, sizeof(s), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+      hipStreamSynchronize(g->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  q->frame_idx = s.frame_idx;
+  if (miss_cnt) {
+    *miss_cnt = s.miss_cnt;
+  }
+  if (!o.found) {
+    return 0;
+  }
+  if (sfn_offset) {
+    *sfn_offset = o.sfn_offset;
+  }
+  if (nof_tx_ports) {
+    *nof_tx_ports = o.nof_tx_ports;
+  }
+  if (bch_payload) {
+    memcpy(bch_payload, o.payload, SRSRAN_BCH_PAYLOAD_LEN);
+  }
+  return 1;
+}
+
+uint32_t bits_value(uint8_t** msg, int n)
+{
+  uint32_t v = 0;
+  for (int i = 0; i < n; i++) {
+    v = (v << 1) | (*(*msg)++ & 1u);
+  }
+  return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+bool srsran_pbch_exists(int nframe, int nslot) { return !(nframe % 5) && nslot == 1; }
+
+int srsran_pbch_put(cf_t* pbch, cf_t* slot1_data, srsran_cell_t cell)
+{
+  const std::vector<uint32_t> re   = pbch_res(cell);
+  const uint32_t              slot = SRSRAN_CP_NSYMB(cell.cp) * 12 * cell.nof_prb;
+  for (size_t i = 0; i < re.size(); i++) {
+    slot1_data[re[i] - slot] = pbch[i];
+  }
+  return (int)re.size();
+}
+
+int srsran_pbch_get(cf_t* slot1_data, cf_t* pbch, srsran_cell_t cell)
+{
+  const std::vector<uint32_t> re   = pbch_res(cell);
+  const uint32_t              slot = SRSRAN_CP_NSYMB(cell.cp) * 12 * cell.nof_prb;
+  for (size_t i = 0; i < re.size(); i++) {
+    pbch[i] = slot1_data[re[i] - slot];
+  }
+  return (int)re.size();
+}
+
+uint32_t srsran_pbch_nof_hypotheses(uint32_t frame_idx)
+{
+  uint32_t n = 0;
+  for (uint32_t r = 0; r < PBCH_FRAME_HYP; r++) {
+    uint32_t nb, dst, src;
+    pbch_hyp_decode(r, nb, dst, src);
+    n += pbch_hyp_valid(frame_idx, nb, src) ? 1u : 0u;
+  }
+  return n;
+}
+
+int srsran_pbch_init(srsran_pbch_t* q)
+{
+  if (!q) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  memset(q, 0, sizeof(*q));
+  q->nof_symbols = PBCH_MAX_SYM;
+  int ndev       = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    fprintf(stderr, "[srsran_pbch] no HIP device\n");
+    return SRSRAN_ERROR;
+  }
+  PbchGpu* g = new PbchGpu();
+  if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
+    g->stream = nullptr;
+    pbch_free_gpu(g);
+    return SRSRAN_ERROR;
+  }
+  const size_t rows = 4 * (size_t)kMaxNre;
+  if (hipMalloc((void**)&g->d_re, PBCH_MAX_SYM * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc((void**)&g->d_seq, kSeqWords * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc((void**)&g->d_hist, 4 * kMaxBits * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&g->d_try, PBCH_NANT_HYP * kMaxBits * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&g->d_hyp, PBCH_HYP * sizeof(PbchHypOut)) != hipSuccess ||
+      hipMalloc((void**)&g->d_state, sizeof(PbchState)) != hipSuccess ||
+      hipMalloc((void**)&g->d_grid, rows * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_ce, SRSRAN_MAX_PORTS * rows * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_noise, sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&g->d_out, sizeof(PbchOut)) != hipSuccess ||
+      hipMemset(g->d_hist, 0, 4 * kMaxBits * sizeof(float)) != hipSuccess ||
+      hipMemset(g->d_try, 0, PBCH_NANT_HYP * kMaxBits * sizeof(float)) != hipSuccess ||
+      hipMemset(g->d_hyp, 0, PBCH_HYP * sizeof(PbchHypOut)) != hipSuccess ||
+      hipMemset(g->d_state, 0, sizeof(PbchState)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    pbch_free_gpu(g);
+    return SRSRAN_ERROR;
+  }
+  q->gpu = g;
+  return SRSRAN_SUCCESS;
+}
+
+void srsran_pbch_free(srsran_pbch_t* q)
+{
+  if (q) {
+    pbch_free_gpu((PbchGpu*)q->gpu);
+    memset(q, 0, sizeof(*q));
+  }
+}
+
+int srsran_pbch_set_cell(srsran_pbch_t* q, srsran_cell_t cell)
+{
+  // srsran_cell_isvalid; 3 ports are refused (the reference accepts them and then never tries a hypothesis)
+  if (!q || !q->gpu || cell.id >= 504 || cell.nof_ports > SRSRAN_MAX_PORTS || cell.nof_ports == 3 || cell.nof_prb < 6 ||
+      cell.nof_prb > SRSRAN_MAX_PRB || (cell.cp != SRSRAN_CP_NORM && cell.cp != SRSRAN_CP_EXT)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  PbchGpu* g = (PbchGpu*)q->gpu;
+  hipDeviceSynchronize();  // no batch reads the tables while they change
+  if (cell.nof_ports == 0) {
+    q->search_all_ports = true;
+    cell.nof_ports      = SRSRAN_MAX_PORTS;
+  } else {
+    q->search_all_ports = false;
+  }
+  if (q->cell.id != cell.id || q->cell.nof_prb == 0) {  // pbch.c:247-252
+    q->cell = cell;
+    std::vector<uint32_t> seq(kSeqWords, 0u);
+    gold_bits(cell.id, cell.cp == SRSRAN_CP_NORM ? 1920 : 1728, seq.data());
+    if (hipMemcpy(g->d_seq, seq.data(), kSeqWords * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+      return SRSRAN_ERROR;
+    }
+  }
+  const std::vector<uint32_t> re = pbch_res(q->cell);
+  q->nof_symbols                 = (uint32_t)re.size();
+  if (re.size() > PBCH_MAX_SYM ||
+      hipMemcpy(g->d_re, re.data(), re.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  g->ready = true;
+  return SRSRAN_SUCCESS;
+}
+
+void srsran_pbch_decode_reset(srsran_pbch_t* q)
+{
+  if (q) {
+    q->frame_idx = 0;
+    if (q->gpu) {
+      set_state(q, &q->frame_idx, nullptr);
+    }
+  }
+}
+
+int srsran_pbch_decode(srsran_pbch_t* q, srsran_chest_dl_res_t* channel, cf_t* sf_symbols[SRSRAN_MAX_PORTS],
+                       uint8_t bch_payload[SRSRAN_BCH_PAYLOAD_LEN], uint32_t* nof_tx_ports, int* sfn_offset)
+{
+  return decode_sync(q, channel, sf_symbols, bch_payload, nof_tx_ports, sfn_offset, false, nullptr);
+}
+
+void srsran_pbch_mib_unpack(uint8_t* msg, srsran_cell_t* cell, uint32_t* sfn)
+{
+  if (!msg || !cell) {
+    return;
+  }
+  const uint32_t bw = bits_value(&msg, 3);
+  cell->nof_prb     = bw == 0 ? 6 : bw == 1 ? 15 : (bw - 1) * 25;
+  cell->phich_length = bits_value(&msg, 1) ? SRSRAN_PHICH_EXT : SRSRAN_PHICH_NORM;
+  switch (bits_value(&msg, 2)) {
+    case 0:
+      cell->phich_resources = SRSRAN_PHICH_R_1_6;
+      break;
+    case 1:
+      cell->phich_resources = SRSRAN_PHICH_R_1_2;
+      break;
+    case 2:
+      cell->phich_resources = SRSRAN_PHICH_R_1;
+      break;
+    default:
+      cell->phich_resources = SRSRAN_PHICH_R_2;
+      break;
+  }
+  if (sfn) {
+    *sfn = bits_value(&msg, 8) << 2;
+  }
+}
+
+int srsran_pbch_gpu_decode_batch(uint32_t nof_entries, const srsran_pbch_gpu_entry_t* entries,
+                                 srsran_pbch_gpu_res_t* d_out, void* stream)
+{
+  if (nof_entries == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!entries || !d_out) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  std::vector<PbchEntry> es(nof_entries);
+  for (uint32_t i = 0; i < nof_entries; i++) {
+    const srsran_pbch_gpu_entry_t& in = entries[i];
+    if (!usable(in.q) || !in.d_grid || !in.d_ce || !in.d_noise || in.ce_row_len == 0 || in.nof_rx == 0 ||
+        in.nof_rx > SRSRAN_MAX_PORTS) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    for (uint32_t j = 0; j < i; j++) {
+      if (entries[j].q == in.q || entries[j].q->gpu == in.q->gpu) {
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
+    }
+    PbchEntry e = object_entry(in.q, false);
+    e.grid      = (const float2*)in.d_grid;
+    e.ce        = (const float2*)in.d_ce;
+    e.noise     = in.d_noise;
+    e.re_off    = 0;
+    e.ce_row    = in.ce_row_len;
+    e.ce_port   = in.nof_rx * in.ce_row_len;
+    es[i]       = e;
+  }
+  PbchGpu* owner = (PbchGpu*)entries[0].q->gpu;
+  owner->h_entries.swap(es);
+  return enqueue(owner, (PbchOut*)d_out, (hipStream_t)stream);
+}
+
+int srsran_pbch_gpu_last_llr(srsran_pbch_t* q, const float** d_llr, uint32_t* nof_llr, uint32_t* frame_idx)
+{
+  if (!q || !q->gpu) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (refresh(q, nullptr) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR;
+  }
+  if (d_llr) {
+    *d_llr = ((PbchGpu*)q->gpu)->d_hist;
+  }
+  if (nof_llr) {
+    *nof_llr = 4 * 2 * q->nof_symbols;
+  }
+  if (frame_idx) {
+    *frame_idx = q->frame_idx;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_pbch_gpu_last_hyp(srsran_pbch_t* q, const void** d_hyp, uint32_t* nof_hyp)
+{
+  if (!q || !q->gpu) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (hipDeviceSynchronize() != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  if (d_hyp) {
+    *d_hyp = ((PbchGpu*)q->gpu)->d_hyp;
+  }
+  if (nof_hyp) {
+    *nof_hyp = PBCH_HYP;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+/* ---------------- ue_mib.c ---------------- */
+
+void srsran_ue_mib_free(srsran_ue_mib_t* q)
+{
+  if (!q) {
+    return;
+  }
+  free(q->sf_symbols);
+  srsran_chest_dl_res_free(&q->chest_res);
+  srsran_chest_dl_free(&q->chest);
+  srsran_pbch_free(&q->pbch);
+  srsran_ofdm_rx_free(&q->fft);
+  memset(q, 0, sizeof(*q));
+}
+
+void srsran_ue_mib_reset(srsran_ue_mib_t* q)
+{
+  if (q) {
+    q->frame_cnt      = 0;
+    q->pbch.frame_idx = 0;
+    if (q->pbch.gpu) {
+      set_state(&q->pbch, &q->pbch.frame_idx, &q->frame_cnt);
+    }
+  }
+}
+
+int srsran_ue_mib_init(srsran_ue_mib_t* q, cf_t* in_buffer, uint32_t max_prb)
+{
+  if (!q || max_prb < 6 || max_prb > SRSRAN_MAX_PRB) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  memset(q, 0, sizeof(*q));
+  if (srsran_pbch_init(&q->pbch)) {
+    return SRSRAN_ERROR;
+  }
+  PbchGpu* g    = (PbchGpu*)q->pbch.gpu;
+  q->sf_symbols = (cf_t*)calloc(SRSRAN_SF_LEN_RE(max_prb, SRSRAN_CP_NORM), sizeof(cf_t));
+  srsran_ofdm_cfg_t cfg;  // srsran_ofdm_rx_init (ofdm.c:263-283)
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.cp         = SRSRAN_CP_NORM;
+  cfg.in_buffer  = in_buffer;
+  cfg.out_buffer = q->sf_symbols;
+  cfg.nof_prb    = max_prb;
+  cfg.sf_type    = SRSRAN_SF_NORM;
+  if (!q->sf_symbols || srsran_ofdm_rx_init_cfg(&q->fft, &cfg) || srsran_chest_dl_init(&q->chest, max_prb, 1) ||
+      srsran_chest_dl_res_init(&q->chest_res, max_prb) ||
+      hipMalloc((void**)&g->d_mib_grid, (size_t)SRSRAN_SF_LEN_RE(max_prb, SRSRAN_CP_NORM) * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_mib_ce, SRSRAN_MAX_PORTS * (size_t)12 * max_prb * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&g->d_mib_res, 4 * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&g->d_mib_sf, sizeof(uint32_t)) != hipSuccess ||
+      hipMemset(g->d_mib_sf, 0, sizeof(uint32_t)) != hipSuccess) {
+    srsran_ue_mib_free(q);
+    return SRSRAN_ERROR;
+  }
+  srsran_ue_mib_reset(q);
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_ue_mib_set_cell(srsran_ue_mib_t* q, srsran_cell_t cell)
+{
+  if (!q || !q->pbch.gpu || cell.nof_ports > SRSRAN_MAX_PORTS || cell.nof_prb > q->fft.max_prb) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  if (srsran_pbch_set_cell(&q->pbch, cell) || srsran_ofdm_rx_set_prb(&q->fft, cell.cp, cell.nof_prb)) {
+    return SRSRAN_ERROR;
+  }
+  if (cell.nof_ports == 0) {
+    cell.nof_ports = SRSRAN_MAX_PORTS;
+  }
+  if (srsran_chest_dl_set_cell(&q->chest, cell)) {
+    return SRSRAN_ERROR;
+  }
+  srsran_ue_mib_reset(q);
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_ue_mib_decode(srsran_ue_mib_t* q, uint8_t bch_payload[SRSRAN_BCH_PAYLOAD_LEN], uint32_t* nof_tx_ports,
+                         int* sfn_offset)
+{
+  if (!q || !usable(&q->pbch)) {
+    return SRSRAN_ERROR;
+  }
+  srsran_ofdm_rx_sf(&q->fft);
+  srsran_dl_sf_cfg_t sf_cfg;  // sf_idx is always 0 in MIB
+  memset(&sf_cfg, 0, sizeof(sf_cfg));
+  cf_t* sf_buffer[SRSRAN_MAX_PORTS] = {};  // the MIB decoder uses a single antenna
+  sf_buffer[0]                      = q->sf_symbols;
+  if (srsran_chest_dl_estimate(&q->chest, &sf_cfg, sf_buffer, &q->chest_res) < 0) {
+    return SRSRAN_ERROR;
+  }
+  // the reset at frame_cnt > 8, the reset on success and the increment on a miss (ue_mib.c:151-169) run on the
+  // device with the decoder (mib_rule), where the batch applies them too
+  const int ret = decode_sync(&q->pbch, &q->chest_res, sf_buffer, bch_payload, nof_tx_ports, sfn_offset, true,
+                              &q->frame_cnt);
+  if (ret < 0) {
+    fprintf(stderr, "[srsran_ue_mib] Error decoding PBCH (%d)\n", ret);
+    return ret;
+  }
+  return ret == 1 ? SRSRAN_UE_MIB_FOUND : SRSRAN_UE_MIB_NOTFOUND;
+}
+
+int srsran_ue_mib_gpu_decode_batch(uint32_t nof_entries, const srsran_ue_mib_gpu_entry_t* entries,
+                                   srsran_pbch_gpu_res_t* d_out, void* stream)
+{
+  if (nof_entries == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!entries || !d_out) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  for (uint32_t i = 0; i < nof_entries; i++) {
+    if (!entries[i].q || !usable(&entries[i].q->pbch) || !entries[i].d_samples ||
+        !((PbchGpu*)entries[i].q->pbch.gpu)->d_mib_grid) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    for (uint32_t j = 0; j < i; j++) {
+      if (entries[j].q == entries[i].q) {
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
+    }
+  }
+  // srsran_chest_dl_estimate's configuration (chest_dl.c:999-1007): AVERAGE, REFS noise, the automatic Gauss filter.
+  // With REFS the filter's width comes from the subframe's own residuals, so the estimate carries no state from
+  // earlier calls and the device rows equal every row of the synchronous call's full-grid estimate.
+  srsran_chest_dl_cfg_t chest_cfg;
+  memset(&chest_cfg, 0, sizeof(chest_cfg));
+  std::vector<PbchEntry> es(nof_entries);
+  for (uint32_t i = 0; i < nof_entries; i++) {
+    srsran_ue_mib_t* m   = entries[i].q;
+    PbchGpu*         g   = (PbchGpu*)m->pbch.gpu;
+    const uint32_t   nre = 12 * m->pbch.cell.nof_prb;
+    if (srsran_ofdm_rx_gpu(&m->fft, entries[i].d_samples, (cf_t*)g->d_mib_grid, 1, 1, 0.0f, stream) ||
+        srsran_chest_dl_gpu_estimate_batch_cfg(&m->chest, &chest_cfg, g->d_mib_sf, 1, (const cf_t*)g->d_mib_grid, 0,
+                                               (cf_t*)g->d_mib_ce, 0, 0, g->d_mib_res, stream)) {
+      return SRSRAN_ERROR;
+    }
+    PbchEntry e = object_entry(&m->pbch, true);
+    e.grid      = g->d_mib_grid;
+    e.ce        = g->d_mib_ce;
+    e.noise     = g->d_mib_res;  // {noise_estimate, rsrp, rssi, cfo}
+    e.re_off    = 0;
+    e.ce_row    = nre;
+    e.ce_port   = nre;
+    es[i]       = e;
+  }
+  PbchGpu* owner = (PbchGpu*)entries[0].q->pbch.gpu;
+  owner->h_entries.swap(es);
+  return enqueue(owner, (PbchOut*)d_out, (hipStream_t)stream);
+}
+
+int srsran_ue_mib_gpu_sync(srsran_ue_mib_t* q)
+{
+  if (!q || !q->pbch.gpu) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return refresh(&q->pbch, &q->frame_cnt);
+}
+
+}  // extern "C"

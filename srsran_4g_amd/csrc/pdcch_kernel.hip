@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ctrl_dev.h"
 #include "pdcch_kernel.h"
 #include "viterbi_dev.h"
 
@@ -27,12 +28,6 @@ namespace {
 #pragma clang fp contract(off)
 
 constexpr float   NSQRT2  = -1.41421356237309504880f;  // (float)(-M_SQRT2)
-constexpr float   RX_NULL = 10000.0f;                  // SRSRAN_RX_NULL
-constexpr int     NCOLS   = 32;
-__constant__ uint8_t kPerm[NCOLS] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31,
-                                     0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
-__constant__ uint8_t kPermInv[NCOLS] = {16, 0, 24, 8, 20, 4, 28, 12, 18, 2, 26, 10, 22, 6, 30, 14,
-                                        17, 1, 25, 9, 21, 5, 29, 13, 19, 3, 27, 11, 23, 7, 31, 15};
 // PCFICH codewords (36.212 Table 5.3.4-1) as bits: cfi c -> 32-bit word, bit i = codeword bit i
 __constant__ uint32_t kCfiWords[3] = {0xB6DB6DB6u, 0x6DB6DB6Du, 0xDB6DB6DBu};
 
@@ -88,17 +83,6 @@ __global__ void pdcch_llr_kernel(const float2* __restrict__ x, uint32_t nbits, c
 // (srsran_predecoding_diversity2_sse, precoding.c:518-643) for the first 4 * (n / 4) symbols when
 // n > 32, the generic loop (precoding.c:428-503) for the rest; the layer demapping
 // (srsran_layerdemap_diversity) is the codeword order d[2k + l] = x_l[k].
-struct cpx {
-  float r, i;
-};
-__device__ __forceinline__ cpx ldc(const float2* p, uint32_t k)
-{
-  const float2 v = p[k];
-  return {v.x, v.y};
-}
-__device__ __forceinline__ cpx cmulf(cpx a, cpx b) { return {a.r * b.r - a.i * b.i, a.i * b.r + a.r * b.i}; }
-__device__ __forceinline__ cpx conjf(cpx a) { return {a.r, -a.i}; }
-
 __global__ void ctrl_diversity_kernel(CtrlEqArgs a)
 {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;  // symbol pair
@@ -147,34 +131,6 @@ __global__ void ctrl_diversity_kernel(CtrlEqArgs a)
 
 __device__ __forceinline__ uint32_t parity32(uint32_t v) { return vit_parity32(v); }
 
-// Rank of soft-buffer position p (stream s, column col, row r) among the non-dummy positions of
-// the circular buffer (rm_conv.c bit collection order); -1 for a dummy position.  Only row 0 of a
-// column whose permuted index is below ndummy (< 32) is a dummy.
-__device__ __forceinline__ int cb_rank(int p, int nrows, int Kp, int ndummy, const uint8_t* dcols_before)
-{
-  const int s = p / Kp, q = p - s * Kp, col = q / nrows, r = q - col * nrows;
-  const bool dcol = kPerm[col] < ndummy;
-  if (r == 0 && dcol) {
-    return -1;
-  }
-  return s * (Kp - ndummy) + col * nrows - dcols_before[col] + r - (dcol ? 1 : 0);
-}
-
-// Soft-buffer position of rank k (inverse of cb_rank).
-__device__ __forceinline__ int cb_pos(int k, int nrows, int Kp, int ndummy)
-{
-  const int nv = Kp - ndummy, s = k / nv;
-  int       r  = k - s * nv;
-  for (int col = 0; col < NCOLS; col++) {
-    const int cnt = nrows - (kPerm[col] < ndummy ? 1 : 0);
-    if (r < cnt) {
-      return s * Kp + col * nrows + r + (kPerm[col] < ndummy ? 1 : 0);
-    }
-    r -= cnt;
-  }
-  return -1;
-}
-
 }  // namespace
 
 // One 64-lane workgroup per candidate.
@@ -185,7 +141,7 @@ __global__ __launch_bounds__(64) void pdcch_cand_kernel(const float* __restrict_
   __shared__ uint16_t sym[3 * (PDCCH_MAX_BITS + 16)];
   __shared__ uint64_t dec[5 * (PDCCH_MAX_BITS + 16) + 6];
   __shared__ uint8_t  data[PDCCH_MAX_BITS + 16];
-  __shared__ uint8_t  dcb[NCOLS];
+  __shared__ uint8_t  dcb[CTRL_NCOLS];
   __shared__ int      skip;
 
   const PdcchCand c    = cands[blockIdx.x];
@@ -213,53 +169,11 @@ __global__ __launch_bounds__(64) void pdcch_cand_kernel(const float* __restrict_
     return;
   }
 
-  // ---- rate de-matching (rm_conv.c:120-175) ----
-  const int nrows = (int)((clen / 3 - 1) / NCOLS + 1);
-  const int Kp    = nrows * NCOLS;
-  const int nd    = max(0, Kp - (int)(clen / 3));
-  const int nv    = 3 * (Kp - nd);  // non-dummy positions of the circular buffer
-  if (lane == 0) {
-    int acc = 0;
-    for (int col = 0; col < NCOLS; col++) {
-      dcb[col] = (uint8_t)acc;
-      acc += kPerm[col] < nd ? 1 : 0;
-    }
-  }
-  __syncthreads();
-  for (uint32_t oi = lane; oi < clen; oi += 64) {
-    const int i = (int)(oi / 3), j = (int)(oi - 3 * (oi / 3));
-    const int di = (i + nd) / NCOLS, dj = (i + nd) % NCOLS;
-    const int p  = Kp * j + kPermInv[dj] * nrows + di;
-    const int rk = cb_rank(p, nrows, Kp, nd, dcb);
-    float     t  = RX_NULL;
-    if (rk >= 0) {
-      for (int k = rk; k < (int)E; k += nv) {
-        if (t == RX_NULL) {
-          t = e[k];
-        } else if (e[k] != RX_NULL) {
-          t = t + e[k];
-        }
-      }
-    }
-    rm[oi] = t != RX_NULL ? t : 0.0f;
-  }
-  __syncthreads();
-
-  // ---- quantisation: gain 500 / max|x|, fused multiply-add as the reference build (viterbi.c:560-575) ----
-  float mx = 0.0f;
-  for (uint32_t i = lane; i < clen; i += 64) {
-    mx = fmaxf(mx, fabsf(rm[i]));
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  }
-  const float mxv  = (mx > 0.0f && __builtin_isnormal(mx)) ? mx : 1e-9f;
-  const float gain = __fdiv_rn(500.0f, mxv);
-  for (uint32_t i = lane; i < clen; i += 64) {
-    int v  = __float2int_rz(__builtin_fmaf(gain, rm[i], 32767.5f));
-    sym[i] = (uint16_t)min(max(v, 0), 65535);
-  }
-  __syncthreads();
+  // ---- rate de-matching (rm_conv.c:120-175) and quantisation (viterbi.c:560-575): ctrl_dev.h ----
+  const RmGeom gm    = rm_geom(clen);
+  const int    nrows = gm.nrows, Kp = gm.Kp, nd = gm.nd, nv = gm.nv;
+  rm_conv_rx_gather(clen, E, [e](int k) { return e[k]; }, rm, dcb, lane);
+  vit_quantise(rm, clen, sym, lane);
 
   // ---- Viterbi, lane = state (viterbi_dev.h) ----
   viterbi37_tb16(sym, F, dec, data, lane);
@@ -292,7 +206,7 @@ __global__ __launch_bounds__(64) void pdcch_cand_kernel(const float* __restrict_
     for (int h = 0; h < 2; h++) {
       const int pos = cb_pos((int)((k + h) % (uint32_t)nv), nrows, Kp, nd);
       const int st  = pos / Kp, q = pos - st * Kp, col = q / nrows, row = q - col * nrows;
-      const int bi  = row * NCOLS + kPerm[col] - nd;  // coded bit index / 3
+      const int bi  = row * CTRL_NCOLS + kPerm[col] - nd;  // coded bit index / 3
       uint32_t  sr  = 0;                              // tail-biting encoder register at bit bi
       for (int t = bi - 6; t <= bi; t++) {
         sr = (sr << 1) | data[(t + (int)F) % (int)F];

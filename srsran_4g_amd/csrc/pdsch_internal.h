@@ -55,5 +55,10 @@ const float2* chest_dl_gpu_last_ce(const srsran_chest_dl_t* q);
 int csi_from_device(const float2* d_ce, size_t row_stride, uint32_t row_len, uint32_t nof_symbols, float noise,
                     srsran_csi_gpu_t* out);
 
+// ---- PBCH (pbch_api.cpp) ----
+// PBCH REs (pbch.c srsran_pbch_cp): grid indices within the subframe, slot 1, symbols 0..3, the 72 central
+// subcarriers; one table for the eNB's transmitter and the UE's decoder
+std::vector<uint32_t> pbch_res(const srsran_cell_t& cell);
+
 }  // namespace srsran_amd
 #endif

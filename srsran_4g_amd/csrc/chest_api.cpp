@@ -15,6 +15,7 @@
 
 #include "../../include/srsran_ue_dl.h"
 #include "chest_kernel.h"
+#include "dev_buf.h"
 #include "pdsch_internal.h"
 #include "ofdm_kernel.h"
 
@@ -45,29 +46,28 @@ void gold(uint32_t c_init, uint8_t* c, uint32_t len)
 
 struct ChestGpu {
   hipStream_t stream  = nullptr;
-  float2*     pilots  = nullptr;  // [sf][pp][4 * CHEST_MAX_NREF]
-  float2*     grid    = nullptr;  // host-synchronous path scratch
-  float2*     ce      = nullptr;
-  float*      stats   = nullptr;  // [rx][port][8]
-  float*      bstats  = nullptr;  // batch path: [sf][CHEST_STATS_PER_SF]
-  float*      bsync   = nullptr;  // batch path, sync correction: [sf][CHEST_SYNC_PER_SF] phase sums
-  float*      bserr   = nullptr;  // batch path, sync correction: [sf][rx * 4 + port] sync errors
-  uint32_t    bstats_cap = 0;
+  DevBuf<float2> pilots;  // [sf][pp][4 * CHEST_MAX_NREF]
+  DevBuf<float2> grid;    // host-synchronous path scratch
+  DevBuf<float2> ce;
+  DevBuf<float>  stats;   // [rx][port][8]
+  DevBuf<float>  bstats;  // batch path: [sf][CHEST_STATS_PER_SF]
+  DevBuf<float>  bsync;   // batch path, sync correction: [sf][CHEST_SYNC_PER_SF] phase sums
+  DevBuf<float>  bserr;   // batch path, sync correction: [sf][rx * 4 + port] sync errors
   uint32_t    max_prb = 0;
   uint32_t    nrx     = 0;
   float       filter[8];
   uint32_t    filter_len = 0;
-  float2*     pss     = nullptr;  // the cell's 62 PSS values (noise PSS)
-  float*      noise   = nullptr;  // device q->noise_estimate [4][4]: host-sync upload / batch state; [16]: the batch
+  DevBuf<float2> pss;     // the cell's 62 PSS values (noise PSS)
+  DevBuf<float> noise;    // device q->noise_estimate [4][4]: host-sync upload / batch state; [16]: the batch
                                   // path's kept CFO (the last subframe with its own estimate)
-  float*      sync    = nullptr;  // correct_sync_error sums [4 rx][4 port][10]
-  float2*     tab     = nullptr;  // sync correction phasor table (12 * max_prb)
+  DevBuf<float> sync;     // correct_sync_error sums [4 rx][4 port][10]
+  DevBuf<float2> tab;     // sync correction phasor table (12 * max_prb)
   float       sync_err[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS] = {};  // q->sync_err (chest_dl.c:776)
   srsran_tdd_config_t tdd{};  // the batch estimators' TDD frame configuration (srsran_chest_dl_gpu_set_tdd_config)
   // MBSFN reference signals per area (q->mbsfn_refs, chest_dl.c:263-278): host tables [10 sf][3][6 nof_prb], the
   // one of area mbsfn_loaded on the device
   std::map<uint16_t, std::vector<float2>> mbsfn;
-  float2* d_mbsfn      = nullptr;
+  DevBuf<float2> d_mbsfn;
   int     mbsfn_loaded = -1;
 };
 
@@ -329,15 +329,11 @@ int srsran_chest_dl_init(srsran_chest_dl_t* q, uint32_t max_prb, uint32_t nof_rx
   g->nrx          = nof_rx_antennas;
   const size_t sf = 14 * 12 * (size_t)max_prb;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&g->pilots, 10 * kPilotsPerSf * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->grid, nof_rx_antennas * sf * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->ce, SRSRAN_MAX_PORTS * nof_rx_antennas * sf * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->stats, SRSRAN_MAX_PORTS * SRSRAN_MAX_PORTS * 8 * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->pss, 62 * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->noise, 17 * sizeof(float)) != hipSuccess || hipMemset(g->noise, 0, 17 * sizeof(float)) ||
-      hipMalloc((void**)&g->sync, 16 * 10 * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->tab, 12 * (size_t)max_prb * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_mbsfn, 10 * 18 * (size_t)max_prb * sizeof(float2)) != hipSuccess) {
+      !g->pilots.reserve(10 * kPilotsPerSf) || !g->grid.reserve(nof_rx_antennas * sf) ||
+      !g->ce.reserve(SRSRAN_MAX_PORTS * nof_rx_antennas * sf) ||
+      !g->stats.reserve(SRSRAN_MAX_PORTS * SRSRAN_MAX_PORTS * 8) || !g->pss.reserve(62) || !g->noise.reserve(17) ||
+      hipMemset(g->noise, 0, 17 * sizeof(float)) || !g->sync.reserve(16 * 10) ||
+      !g->tab.reserve(12 * (size_t)max_prb) || !g->d_mbsfn.reserve(10 * 18 * (size_t)max_prb)) {
     q->gpu = g;
     srsran_chest_dl_free(q);
     return SRSRAN_ERROR;
@@ -358,18 +354,6 @@ void srsran_chest_dl_free(srsran_chest_dl_t* q)
       hipStreamSynchronize(g->stream);
       hipStreamDestroy(g->stream);
     }
-    hipFree(g->pilots);
-    hipFree(g->grid);
-    hipFree(g->ce);
-    hipFree(g->stats);
-    hipFree(g->bstats);
-    hipFree(g->bsync);
-    hipFree(g->bserr);
-    hipFree(g->pss);
-    hipFree(g->noise);
-    hipFree(g->sync);
-    hipFree(g->tab);
-    hipFree(g->d_mbsfn);
     delete g;
   }
   memset(q, 0, sizeof(*q));
@@ -875,19 +859,13 @@ int estimate_batch(srsran_chest_dl_t*           q,
     return SRSRAN_ERROR;
   }
   ChestGpu* g = (ChestGpu*)q->gpu;
-  if (nsf > g->bstats_cap) {
+  if ((size_t)nsf * CHEST_STATS_PER_SF > g->bstats.cap() || (size_t)nsf * CHEST_SYNC_PER_SF > g->bsync.cap() ||
+      (size_t)nsf * 16 > g->bserr.cap()) {
     hipStreamSynchronize((hipStream_t)stream);  // the previous batch may still use them
-    hipFree(g->bstats);
-    hipFree(g->bsync);
-    hipFree(g->bserr);
-    g->bstats = g->bsync = g->bserr = nullptr;
-    g->bstats_cap = 0;
-    if (hipMalloc((void**)&g->bstats, nsf * CHEST_STATS_PER_SF * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&g->bsync, nsf * CHEST_SYNC_PER_SF * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&g->bserr, nsf * 16 * sizeof(float)) != hipSuccess) {
+    if (!g->bstats.reserve((size_t)nsf * CHEST_STATS_PER_SF) || !g->bsync.reserve((size_t)nsf * CHEST_SYNC_PER_SF) ||
+        !g->bserr.reserve((size_t)nsf * 16)) {
       return SRSRAN_ERROR;
     }
-    g->bstats_cap = nsf;
   }
   hipStream_t s = (hipStream_t)stream;
   ChestArgs   a{};

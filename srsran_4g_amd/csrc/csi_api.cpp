@@ -9,6 +9,7 @@
 
 #include "../../include/srsran_ue_dl.h"
 #include "csi_kernel.h"
+#include "dev_buf.h"
 #include "pdsch_internal.h"
 
 using namespace srsran_amd;
@@ -17,14 +18,14 @@ namespace {
 
 // scratch of the host-pointer calls: four estimate rows and one record, kept for the process
 struct CsiScratch {
-  std::mutex        mu;
-  float2*           d_h   = nullptr;
-  size_t            cap   = 0;  // float2 a row
-  srsran_csi_gpu_t* d_out = nullptr;
+  std::mutex               mu;
+  DevBuf<float2>           d_h;      // four rows of cap
+  size_t                   cap = 0;  // float2 a row
+  DevBuf<srsran_csi_gpu_t> d_out;
 };
 CsiScratch& scratch()
 {
-  static CsiScratch s;
+  static auto& s = *new CsiScratch;  // never destroyed: no hipFree after the runtime is gone
   return s;
 }
 
@@ -34,17 +35,13 @@ int csi_run(const float2* d_ce, cf_t* h[SRSRAN_MAX_PORTS][SRSRAN_MAX_PORTS], siz
 {
   CsiScratch&                 s = scratch();
   std::lock_guard<std::mutex> lock(s.mu);
-  if (!s.d_out && hipMalloc((void**)&s.d_out, sizeof(srsran_csi_gpu_t)) != hipSuccess) {
-    s.d_out = nullptr;
+  if (!s.d_out.reserve(1)) {
     return SRSRAN_ERROR;
   }
   if (!d_ce) {
     if (nof_symbols > s.cap) {
-      hipFree(s.d_h);
-      s.d_h = nullptr;
       s.cap = 0;
-      if (hipMalloc((void**)&s.d_h, 4 * (size_t)nof_symbols * sizeof(float2)) != hipSuccess) {
-        s.d_h = nullptr;
+      if (!s.d_h.reserve(4 * (size_t)nof_symbols)) {
         return SRSRAN_ERROR;
       }
       s.cap = nof_symbols;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/srsran_enb_dl.h"
+#include "dev_buf.h"
 #include "llr_kernel.h"
 #include "pdsch_internal.h"
 
@@ -25,28 +26,21 @@ struct EnbDlGpu {
   srsran_sch_t  sch{};
   srsran_ofdm_t ofdm{};
   uint32_t      N = 0, sf_len = 0;
-  float2*       d_grid = nullptr;  // [sf][port][2 nsymb][nre]
-  size_t        grid_cap = 0;
-  uint8_t*      d_e = nullptr;     // packed e bits of every codeword
-  size_t        e_cap = 0;
-  uint32_t*     d_idx = nullptr;   // RE tables of every subframe
-  size_t        idx_cap = 0;
-  uint32_t      last_sf = 0;    // subframes in d_grid (srsran_enb_dl_gpu_sf_symbols)
-  PdschTx*      d_items = nullptr;
-  size_t        items_cap = 0;
-  uint32_t*     d_sfidx = nullptr;
-  size_t        sfidx_cap = 0;
+  DevBuf<float2>   d_grid;      // [sf][port][2 nsymb][nre]
+  DevBuf<uint8_t>  d_e;         // packed e bits of every codeword
+  uint32_t         last_sf = 0; // subframes in d_grid (srsran_enb_dl_gpu_sf_symbols)
+  DevBuf<PdschTx>  d_items;
+  DevBuf<uint32_t> d_sfidx;
   // RE tables on the device, keyed by (PRB allocation, symbols a slot, first symbol, subframe): built
   // once, not re-uploaded every batch
-  std::unordered_map<std::string, std::pair<uint32_t*, uint32_t>> tabs;
+  std::unordered_map<std::string, std::pair<DevBuf<uint32_t>, uint32_t>> tabs;
   // control channels: REG tables of the cell, the PBCH REs, the PSS / SSS sequences (built at init)
   srsran_regs_t regs{};
   bool          regs_ok = false;
-  uint32_t*     d_ctab  = nullptr;  // [16 PCFICH][PBCH][PDCCH CFI 1][CFI 2][CFI 3]
+  DevBuf<uint32_t> d_ctab;          // [16 PCFICH][PBCH][PDCCH CFI 1][CFI 2][CFI 3]
   uint32_t      pbch_off = 16, pbch_nsym = 0, pdcch_off[3] = {0, 0, 0};
-  float2*       d_sync  = nullptr;  // [PSS 72][SSS subframe 0: 72][SSS subframe 5: 72] (5 zero guards each side)
-  CtrlTxJob*    d_jobs  = nullptr;
-  size_t        jobs_cap = 0;
+  DevBuf<float2> d_sync;            // [PSS 72][SSS subframe 0: 72][SSS subframe 5: 72] (5 zero guards each side)
+  DevBuf<CtrlTxJob> d_jobs;
   srsran_phich_t phich{};  // PHICH transmitter on `regs` (created with the first subframe that carries one)
   bool           phich_ok = false;
 };
@@ -60,9 +54,6 @@ void tab_evict(EnbDlGpu* g, uint32_t nof_sf)
 {
   if (g->tabs.size() + nof_sf > kTabCache) {
     hipDeviceSynchronize();
-    for (auto& kv : g->tabs) {
-      hipFree(kv.second.first);
-    }
     g->tabs.clear();
   }
 }
@@ -83,31 +74,16 @@ std::pair<uint32_t*, uint32_t> get_tab(EnbDlGpu* g, const srsran_cell_t& cell, c
   key.push_back((char)sf_idx);
   auto it = g->tabs.find(key);
   if (it != g->tabs.end()) {
-    return it->second;
+    return {it->second.first.get(), it->second.second};
   }
   const std::vector<uint32_t> t = pdsch_re_table(cell, gr, lstart, sf_idx);
-  uint32_t*                   d = nullptr;
-  if (hipMalloc((void**)&d, std::max<size_t>(t.size(), 1) * sizeof(uint32_t)) != hipSuccess ||
+  DevBuf<uint32_t>            d;
+  if (!d.reserve(std::max<size_t>(t.size(), 1)) ||
       hipMemcpy(d, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(d);
     return {nullptr, 0};
   }
-  return g->tabs[key] = std::make_pair(d, (uint32_t)t.size());
-}
-
-bool grow(void** p, size_t* cap, size_t need)
-{
-  if (need <= *cap) {
-    return true;
-  }
-  hipFree(*p);
-  *p   = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, need) != hipSuccess) {
-    return false;
-  }
-  *cap = need;
-  return true;
+  auto& e = g->tabs[key] = std::make_pair(std::move(d), (uint32_t)t.size());
+  return {e.first.get(), e.second};
 }
 
 
@@ -176,9 +152,9 @@ bool ctrl_init(EnbDlGpu* g, const srsran_cell_t& cell)
   }
   std::vector<float2> sync;
   sync_sequences(cell.id, sync);
-  return hipMalloc((void**)&g->d_ctab, tab.size() * sizeof(uint32_t)) == hipSuccess &&
+  return g->d_ctab.reserve(tab.size()) &&
          hipMemcpy(g->d_ctab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMalloc((void**)&g->d_sync, sync.size() * sizeof(float2)) == hipSuccess &&
+         g->d_sync.reserve(sync.size()) &&
          hipMemcpy(g->d_sync, sync.data(), sync.size() * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess;
 }
 
@@ -307,22 +283,11 @@ void srsran_enb_dl_gpu_free(srsran_enb_dl_gpu_t* q)
     hipDeviceSynchronize();
     srsran_sch_free(&g->sch);
     srsran_ofdm_tx_free(&g->ofdm);
-    hipFree(g->d_grid);
-    hipFree(g->d_e);
-    hipFree(g->d_idx);
-    hipFree(g->d_items);
-    hipFree(g->d_sfidx);
-    hipFree(g->d_ctab);
-    hipFree(g->d_sync);
-    hipFree(g->d_jobs);
     if (g->phich_ok) {
       srsran_phich_free(&g->phich);
     }
     if (g->regs_ok) {
       srsran_regs_free(&g->regs);
-    }
-    for (auto& kv : g->tabs) {
-      hipFree(kv.second.first);
     }
     delete g;
   }
@@ -433,9 +398,8 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
     npd++;
   }
   const size_t grid_bytes = (size_t)nof_sf * P * nre_sf * sizeof(float2);
-  if (!grow((void**)&g->d_grid, &g->grid_cap, grid_bytes) || !grow((void**)&g->d_e, &g->e_cap, e_tot + 16) ||
-      !grow((void**)&g->d_items, &g->items_cap, nof_sf * sizeof(PdschTx)) ||
-      !grow((void**)&g->d_sfidx, &g->sfidx_cap, nof_sf * sizeof(uint32_t))) {
+  if (!g->d_grid.reserve((size_t)nof_sf * P * nre_sf) || !g->d_e.reserve(e_tot + 16) || !g->d_items.reserve(nof_sf) ||
+      !g->d_sfidx.reserve(nof_sf)) {
     return SRSRAN_ERROR;
   }
   // device pointers of the codewords, tables and grids
@@ -467,7 +431,7 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
       return SRSRAN_ERROR;
     }
   }
-  if (!grow((void**)&g->d_jobs, &g->jobs_cap, std::max<size_t>(jobs.size(), 1) * sizeof(CtrlTxJob))) {
+  if (!g->d_jobs.reserve(std::max<size_t>(jobs.size(), 1))) {
     return SRSRAN_ERROR;
   }
   // HARQ indicators of every subframe: one launch after the grid clear (their REs are no other channel's)
@@ -512,13 +476,13 @@ int srsran_enb_dl_gpu_tx_batch(srsran_enb_dl_gpu_t*          q,
     return SRSRAN_ERROR;
   }
   if (!hi.empty()) {
-    if (int r = srsran_phich_gpu_encode_batch(&g->phich, (uint32_t)hi.size(), hi.data(), nof_sf, (cf_t*)g->d_grid, st)) {
+    if (int r = srsran_phich_gpu_encode_batch(&g->phich, (uint32_t)hi.size(), hi.data(), nof_sf, (cf_t*)g->d_grid.get(), st)) {
       return r;
     }
   }
   g->last_sf = nof_sf;
   const float sc = scale > 0.0f ? scale : 0.05f / sqrtf((float)cell.nof_prb);  // enb_dl_get_norm_factor
-  return srsran_ofdm_tx_gpu(&g->ofdm, (const cf_t*)g->d_grid, d_samples, P, nof_sf, sc, st);
+  return srsran_ofdm_tx_gpu(&g->ofdm, (const cf_t*)g->d_grid.get(), d_samples, P, nof_sf, sc, st);
 }
 
 // ---------------- enb_dl.h: the reference's per-subframe object over the batched transmitter ----------------
@@ -534,10 +498,8 @@ struct EnbDlRef {
   std::vector<srsran_dci_msg_t> dci;
   std::vector<srsran_enb_dl_gpu_phich_t> phich;
   srsran_pdsch_cfg_t            cfg{};
-  uint8_t*                      d_data[SRSRAN_MAX_CODEWORDS] = {nullptr, nullptr};
-  size_t                        data_cap = 0;
-  cf_t*                         d_samples = nullptr;
-  size_t                        samples_cap = 0;
+  DevBuf<uint8_t>               d_data[SRSRAN_MAX_CODEWORDS];  // the largest TB so far + 64 bytes each
+  DevBuf<cf_t>                  d_samples;
   uint32_t                      max_prb = 0;
 };
 
@@ -594,10 +556,6 @@ void srsran_enb_dl_free(srsran_enb_dl_t* q)
       hipStreamDestroy(g->stream);
     }
     enb_ref_release(g);
-    for (auto& d : g->d_data) {
-      hipFree(d);
-    }
-    hipFree(g->d_samples);
     delete g;
   }
   if (q->cell.nof_prb) {
@@ -744,19 +702,13 @@ int srsran_enb_dl_put_pdsch(srsran_enb_dl_t* q, srsran_pdsch_cfg_t* pdsch, uint8
       need = std::max(need, (size_t)pdsch->grant.tb[t].tbs / 8);
     }
   }
-  if (need > g->data_cap) {
-    hipStreamSynchronize(g->stream);
-    for (auto& d : g->d_data) {
-      hipFree(d);
-      d = nullptr;
-    }
-    g->data_cap = 0;
-    for (auto& d : g->d_data) {
-      if (hipMalloc((void**)&d, need + 64) != hipSuccess) {
+  for (auto& d : g->d_data) {
+    if (need && need + 64 > d.cap()) {
+      hipStreamSynchronize(g->stream);
+      if (!d.reserve(need + 64)) {
         return SRSRAN_ERROR;
       }
     }
-    g->data_cap = need;
   }
   hipStreamSynchronize(g->stream);  // the previous subframe's encoder is done with the payload buffers
   for (uint32_t t = 0; t < SRSRAN_MAX_CODEWORDS; t++) {
@@ -787,16 +739,9 @@ void srsran_enb_dl_gen_signal(srsran_enb_dl_t* q)
   if (!g->base) {
     fprintf(stderr, "[srsran_enb_dl] srsran_enb_dl_put_base was not called for this subframe\n");
   }
-  const size_t bytes = (size_t)P * sf_len * sizeof(cf_t);
-  if (bytes > g->samples_cap) {
-    hipFree(g->d_samples);
-    g->d_samples   = nullptr;
-    g->samples_cap = 0;
-    if (hipMalloc((void**)&g->d_samples, bytes) != hipSuccess) {
-      fprintf(stderr, "[srsran_enb_dl] device allocation failed\n");
-      return;
-    }
-    g->samples_cap = bytes;
+  if (!g->d_samples.reserve((size_t)P * sf_len)) {
+    fprintf(stderr, "[srsran_enb_dl] device allocation failed\n");
+    return;
   }
   srsran_enb_dl_gpu_ctrl_t ctrl;
   memset(&ctrl, 0, sizeof(ctrl));
@@ -843,7 +788,7 @@ float srsran_enb_dl_get_maximum_signal_power_dBfs(uint32_t nof_prb)
 
 const cf_t* srsran_enb_dl_gpu_sf_symbols(srsran_enb_dl_gpu_t* q)
 {
-  return q && q->gpu && ((EnbDlGpu*)q->gpu)->last_sf ? (const cf_t*)((EnbDlGpu*)q->gpu)->d_grid : nullptr;
+  return q && q->gpu && ((EnbDlGpu*)q->gpu)->last_sf ? (const cf_t*)((EnbDlGpu*)q->gpu)->d_grid.get() : nullptr;
 }
 
 void srsran_pbch_mib_pack(srsran_cell_t* cell, uint32_t sfn, uint8_t* payload)

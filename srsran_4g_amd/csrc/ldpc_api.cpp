@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/srsran_ldpc.h"
+#include "dev_buf.h"
 #include "ldpc_internal.h"
 
 #include "ldpc_bg_tables.inc"
@@ -69,15 +70,15 @@ bool graph(int bg, int ls, Graph& g)
 
 struct Ctx {
   hipStream_t stream    = nullptr;
-  uint32_t*   d_sh      = nullptr;
-  int8_t*     d_in      = nullptr;  // single-codeword staging of the host-synchronous calls
-  uint8_t*    d_out     = nullptr;
-  uint8_t*    d_ret     = nullptr;
-  uint8_t*    d_lut     = nullptr;  // scale(m), m = 0..127
+  DevBuf<uint32_t> d_sh;
+  DevBuf<int8_t>   d_in;   // single-codeword staging of the host-synchronous calls
+  DevBuf<uint8_t>  d_out;
+  DevBuf<uint8_t>  d_ret;
+  DevBuf<uint8_t>  d_lut;  // scale(m), m = 0..127
   int         bits       = 8;  // LLR / message width: 8 (C, C_AVX2, C_AVX512) or 16 (S)
   int         scale_mode = LDPC_SCALE_SIMD;
   int         sf         = 0;
-  std::map<uint64_t, uint32_t*> xpow;  // (poly, order) -> x^n mod P, n = 0 .. liftK
+  std::map<uint64_t, DevBuf<uint32_t>> xpow;  // (poly, order) -> x^n mod P, n = 0 .. liftK
 };
 
 // x^n mod P for n = 0 .. nmax (P with its x^order bit)
@@ -99,15 +100,8 @@ void free_ctx(Ctx* c)
   if (!c) {
     return;
   }
-  for (auto& kv : c->xpow) {
-    hipFree(kv.second);
-  }
-  hipFree(c->d_sh);
-  hipFree(c->d_in);
-  hipFree(c->d_out);
-  hipFree(c->d_ret);
-  hipFree(c->d_lut);
   if (c->stream) {
+    hipStreamSynchronize(c->stream);  // the buffers go with `delete c`, after the stream
     hipStreamDestroy(c->stream);
   }
   delete c;
@@ -130,14 +124,11 @@ const uint32_t* xpow_for(srsran_ldpc_decoder_t* q, const srsran_crc_t* crc)
     return it->second;
   }
   const auto t = xpow_table((uint32_t)crc->polynom, crc->order, q->liftK);
-  uint32_t*  d = nullptr;
-  if (hipMalloc(&d, t.size() * 4) != hipSuccess ||
-      hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(d);
+  DevBuf<uint32_t> d;
+  if (!d.reserve(t.size()) || hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
     return nullptr;
   }
-  c->xpow[key] = d;
-  return d;
+  return c->xpow[key] = std::move(d);
 }
 
 // ldpc_decoder.c:48-70: clamp the rate-matched length and derive the processed layers
@@ -369,10 +360,9 @@ int srsran_ldpc_decoder_init(srsran_ldpc_decoder_t* q, const srsran_ldpc_decoder
     lut[m] = (uint8_t)(scale_mode == LDPC_SCALE_SIMD ? ((uint32_t)m * (uint32_t)c->sf) >> 16 : m * c->sf / 100);
   }
   const size_t n = ((size_t)q->liftN - 2u * q->ls) * (size_t)(bits / 8);
-  if (hipMalloc(&c->d_lut, 128) != hipSuccess || hipMemcpy(c->d_lut, lut, 128, hipMemcpyHostToDevice) != hipSuccess ||
+  if (!c->d_lut.reserve(128) || hipMemcpy(c->d_lut, lut, 128, hipMemcpyHostToDevice) != hipSuccess ||
       hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&c->d_sh, sh.size() * 4) != hipSuccess || hipMalloc(&c->d_in, n) != hipSuccess ||
-      hipMalloc(&c->d_out, q->liftK) != hipSuccess || hipMalloc(&c->d_ret, 64) != hipSuccess ||
+      !c->d_sh.reserve(sh.size()) || !c->d_in.reserve(n) || !c->d_out.reserve(q->liftK) || !c->d_ret.reserve(64) ||
       hipMemcpy(c->d_sh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
     fprintf(stderr, "[srsran_4g_amd] LDPC: no HIP device / allocation failed\n");
     (void)hipGetLastError();

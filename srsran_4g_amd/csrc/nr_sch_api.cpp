@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/srsran_sch_nr.h"
+#include "dev_buf.h"
 #include "ldpc_internal.h"
 #include "nr_sch_kernel.h"
 
@@ -162,8 +163,7 @@ int Nref(uint32_t nof_prb, srsran_mcs_table_t table, uint32_t max_mimo_layers)  
 
 // pinned host staging of one descriptor upload and the event that marks it consumed
 struct Stage {
-  uint8_t*   h    = nullptr;
-  size_t     cap  = 0;
+  PinBuf<uint8_t> h;
   hipEvent_t ev   = nullptr;
   bool       used = false;
 };
@@ -173,20 +173,16 @@ struct Ctx {
   srsran_sch_nr_args_t        args{};
   srsran_ldpc_decoder_type_t  dtype  = SRSRAN_LDPC_DECODER_C_AVX2;
   std::map<uint32_t, srsran_ldpc_decoder_t*> dec;  // key: bg << 16 | Z
-  uint32_t*                   d_xpow[3] = {};      // CRC24B, CRC24A, CRC16: x^n mod P, n <= 8448
+  DevBuf<uint32_t>            d_xpow[3];           // CRC24B, CRC24A, CRC16: x^n mod P, n <= 8448
   // scratch (grown on demand)
-  uint8_t*  d_desc  = nullptr;  // descriptors of the last batch: NrRmCb[] | LdpcCw[] | NrTb[]
-  size_t    cap_desc = 0;
-  Stage     stage[2];
-  int       cur = 0;
-  uint32_t* d_tbscr = nullptr;  // 2 dwords per TB, zero between launches (nr_tb_kernel clears them)
-  size_t    cap_scr = 0;
-  uint8_t*  d_iters = nullptr;
-  size_t    cap_it = 0;
-  int8_t*   d_e     = nullptr;  // host-synchronous calls: staged LLRs / payload / results
-  uint8_t*  d_pl    = nullptr;
-  uint8_t*  d_res   = nullptr;
-  size_t    cap_e = 0, cap_pl = 0;
+  DevBuf<uint8_t>  d_desc;   // descriptors of the last batch: NrRmCb[] | LdpcCw[] | NrTb[]
+  Stage            stage[2];
+  int              cur = 0;
+  DevBuf<uint32_t> d_tbscr;  // 2 dwords per TB, zero between launches (nr_tb_kernel clears them)
+  DevBuf<uint8_t>  d_iters;
+  DevBuf<int8_t>   d_e;      // host-synchronous calls: staged LLRs / payload / results
+  DevBuf<uint8_t>  d_pl;
+  DevBuf<uint8_t>  d_res;
 };
 
 srsran_ldpc_decoder_t* decoder(Ctx* c, srsran_basegraph_t bg, uint32_t Z)
@@ -209,22 +205,6 @@ srsran_ldpc_decoder_t* decoder(Ctx* c, srsran_basegraph_t bg, uint32_t Z)
   }
   c->dec[key] = q;
   return q;
-}
-
-template <typename T>
-bool grow(T*& p, size_t& cap, size_t n)
-{
-  if (n <= cap) {
-    return true;
-  }
-  hipFree(p);
-  p   = nullptr;
-  cap = 0;
-  if (hipMalloc((void**)&p, sizeof(T) * n) != hipSuccess) {
-    return false;
-  }
-  cap = n;
-  return true;
 }
 
 // the ldpc_rm.c init_rm parameters (ldpc_rm.c:99-160)
@@ -334,14 +314,14 @@ int decode_batch(srsran_sch_nr_t* q, uint32_t n, const srsran_sch_nr_gpu_tb_t* i
   const size_t sz_rm = (sizeof(NrRmCb) * total_cb + 15) & ~size_t(15);
   const size_t sz_cw = (sizeof(LdpcCw) * total_cb + 15) & ~size_t(15);
   const size_t sz_tb = sizeof(NrTb) * n;
-  if (!grow(c->d_desc, c->cap_desc, sz_rm + sz_cw + sz_tb) || !grow(c->d_iters, c->cap_it, total_cb)) {
+  if (!c->d_desc.reserve(sz_rm + sz_cw + sz_tb) || !c->d_iters.reserve(total_cb)) {
     return SRSRAN_ERROR;
   }
-  NrRmCb* d_rm = reinterpret_cast<NrRmCb*>(c->d_desc);
+  NrRmCb* d_rm = reinterpret_cast<NrRmCb*>(c->d_desc.get());
   LdpcCw* d_cw = reinterpret_cast<LdpcCw*>(c->d_desc + sz_rm);
   NrTb*   d_tb = reinterpret_cast<NrTb*>(c->d_desc + sz_rm + sz_cw);
-  if (n * 2 > c->cap_scr) {
-    if (!grow(c->d_tbscr, c->cap_scr, n * 2) || hipMemset(c->d_tbscr, 0, n * 2 * sizeof(uint32_t)) != hipSuccess) {
+  if (n * 2 > c->d_tbscr.cap()) {
+    if (!c->d_tbscr.reserve(n * 2) || hipMemset(c->d_tbscr, 0, n * 2 * sizeof(uint32_t)) != hipSuccess) {
       return SRSRAN_ERROR;
     }
   }
@@ -370,14 +350,8 @@ int decode_batch(srsran_sch_nr_t* q, uint32_t n, const srsran_sch_nr_gpu_tb_t* i
     return SRSRAN_ERROR;
   }
   const size_t total = sz_rm + sz_cw + sz_tb;
-  if (total > st.cap) {
-    hipHostFree(st.h);
-    st.h   = nullptr;
-    st.cap = 0;
-    if (hipHostMalloc((void**)&st.h, total, hipHostMallocDefault) != hipSuccess) {
-      return SRSRAN_ERROR;
-    }
-    st.cap = total;
+  if (!st.h.reserve(total)) {
+    return SRSRAN_ERROR;
   }
   if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) {
     return SRSRAN_ERROR;
@@ -420,10 +394,7 @@ int decode_sync(srsran_sch_nr_t* q, const srsran_sch_cfg_t* cfg, const srsran_sc
   }
   Ctx*         c  = static_cast<Ctx*>(q->gpu);
   const size_t ne = tb->nof_bits, npl = (size_t)(tb->tbs > 0 ? tb->tbs : 0) / 8 + 8;
-  if (!grow(c->d_e, c->cap_e, ne + 64) || !grow(c->d_pl, c->cap_pl, npl)) {
-    return SRSRAN_ERROR;
-  }
-  if (!c->d_res && hipMalloc((void**)&c->d_res, 16) != hipSuccess) {
+  if (!c->d_e.reserve(ne + 64) || !c->d_pl.reserve(npl) || !c->d_res.reserve(16)) {
     return SRSRAN_ERROR;
   }
   if (hipMemcpyAsync(c->d_e, e_bits, ne, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
@@ -544,7 +515,7 @@ int srsran_sch_nr_init_rx(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args)
   bool           ok       = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
   for (int i = 0; ok && i < 3; i++) {
     const auto t = ldpc_xpow_table(polys[i], ords[i], SRSRAN_LDPC_MAX_LEN_CB + 8);
-    ok           = hipMalloc((void**)&c->d_xpow[i], t.size() * 4) == hipSuccess &&
+    ok           = c->d_xpow[i].reserve(t.size()) &&
          hipMemcpy(c->d_xpow[i], t.data(), t.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
   }
   q->gpu = c;
@@ -575,23 +546,14 @@ void srsran_sch_nr_free(srsran_sch_nr_t* q)
       srsran_ldpc_decoder_free(kv.second);
       delete kv.second;
     }
-    for (auto* p : c->d_xpow) {
-      hipFree(p);
-    }
-    hipFree(c->d_desc);
     for (auto& st : c->stage) {
       if (st.ev) {
         hipEventSynchronize(st.ev);
         hipEventDestroy(st.ev);
       }
-      hipHostFree(st.h);
     }
-    hipFree(c->d_tbscr);
-    hipFree(c->d_iters);
-    hipFree(c->d_e);
-    hipFree(c->d_pl);
-    hipFree(c->d_res);
     if (c->stream) {
+      hipStreamSynchronize(c->stream);  // the buffers go with `delete c`, after the stream
       hipStreamDestroy(c->stream);
     }
     delete c;

@@ -15,6 +15,7 @@
 
 #include "../../include/srsran_ue_dl.h"
 #include "stage_copy.h"
+#include "dev_buf.h"
 #include "devkey.h"
 #include "ofdm_kernel.h"
 
@@ -50,8 +51,7 @@ const float2* twiddles(uint32_t N)
 // srsran_vec_apply_cfo's phasor table for one (frequency, length), rebuilt on the launch stream only when the
 // frequency changes (the reference recomputes it every call: SRSRAN_CFO_USE_EXP_TABLE is 0, cfo.c:33)
 struct CfoTab {
-  float2*    d     = nullptr;
-  size_t     cap   = 0;
+  DevBuf<float2> d;
   uint32_t   bits  = 0;  // the float's bit pattern
   uint32_t   len   = 0;
   bool       valid = false;
@@ -59,8 +59,6 @@ struct CfoTab {
   hipEvent_t built = nullptr;  // the launch that wrote d
   hipStream_t built_on = nullptr;
 };
-
-bool grow(void** p, size_t* cap, size_t need);
 
 const float2* cfo_table(CfoTab& t, float f, uint32_t len, hipStream_t s)
 {
@@ -79,9 +77,9 @@ const float2* cfo_table(CfoTab& t, float f, uint32_t len, hipStream_t s)
   if (t.valid) {
     hipStreamWaitEvent(s, t.used, 0);  // a launch on another stream may still read the old table
   }
-  if (len * sizeof(float2) > t.cap) {
+  if (len > t.d.cap()) {
     hipEventSynchronize(t.used);
-    if (!grow((void**)&t.d, &t.cap, len * sizeof(float2))) {
+    if (!t.d.reserve(len)) {
       return nullptr;
     }
   }
@@ -101,7 +99,6 @@ const float2* cfo_table(CfoTab& t, float f, uint32_t len, hipStream_t s)
 
 void cfo_table_free(CfoTab& t)
 {
-  hipFree(t.d);
   if (t.used) {
     hipEventDestroy(t.used);
   }
@@ -115,9 +112,7 @@ uint32_t cp_len(uint32_t c, uint32_t N) { return (uint32_t)ceilf((float)c * (flo
 
 struct OfdmGpu {
   hipStream_t stream = nullptr;
-  float2*     d_in   = nullptr;
-  float2*     d_out  = nullptr;
-  size_t      in_cap = 0, out_cap = 0;
+  DevBuf<float2> d_in, d_out;
   OfdmArgs    proto{};
   CfoTab      cfo;
   bool        mbsfn = false;  // cfg.sf_type == SRSRAN_SF_MBSFN (ofdm.c:219-225)
@@ -126,15 +121,11 @@ struct OfdmGpu {
   // reference's "shall not be called during run-time")
   bool        dc_skip  = true;     // the DFT plan's dc flag (srsran_dft_plan_set_dc): the DC bin carries nothing
   uint32_t    win_n    = 0;        // window_offset_n
-  float2*     d_wo     = nullptr;  // window_offset_buffer [N]
-  size_t      wo_cap   = 0;
-  float2*     d_ph     = nullptr;  // [0, 2 nsymb): RX conj(phase_compensation), [2 nsymb, 4 nsymb): TX phase_compensation
-  size_t      ph_cap   = 0;
+  DevBuf<float2> d_wo;           // window_offset_buffer [N]
+  DevBuf<float2> d_ph;           // [0, 2 nsymb): RX conj(phase_compensation), [2 nsymb, 4 nsymb): TX phase_compensation
   bool        ph_on    = false;
-  float2*     d_shift  = nullptr;  // shift_buffer [sf_sz]
-  size_t      shift_cap = 0;
-  float2*     d_comb   = nullptr;  // a CFO table times shift_buffer (srsran_ofdm_rx_gpu with both)
-  size_t      comb_cap = 0;
+  DevBuf<float2> d_shift;        // shift_buffer [sf_sz]
+  DevBuf<float2> d_comb;         // a CFO table times shift_buffer (srsran_ofdm_rx_gpu with both)
   bool        shift_on = false;
 };
 
@@ -155,25 +146,10 @@ void mbsfn_offsets(uint32_t N, uint32_t nr, uint32_t* off)
   }
 }
 
-bool grow(void** p, size_t* cap, size_t need)
+bool upload(DevBuf<float2>& d, const std::vector<float2>& h)
 {
-  if (*cap >= need) {
-    return true;
-  }
-  hipFree(*p);
-  *p = nullptr;
-  if (hipMalloc(p, need) != hipSuccess) {
-    *cap = 0;
-    return false;
-  }
-  *cap = need;
-  return true;
-}
-
-bool upload(float2** d, size_t* cap, const std::vector<float2>& h)
-{
-  return grow((void**)d, cap, h.size() * sizeof(float2)) &&
-         hipMemcpy(*d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess;
+  return d.reserve(h.size()) &&
+         hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 // each symbol's cyclic prefix length, as SRSRAN_CP_LEN_NORM(i % nsymb) / SRSRAN_CP_LEN_EXT
@@ -191,7 +167,7 @@ int build_window(OfdmGpu* g)
     const float y = (float)(M_PI * 2.0 * (double)(float)g->win_n * (double)(float)i / (double)(float)N);
     h[i]          = make_float2(cosf(y), sinf(y));
   }
-  return upload(&g->d_wo, &g->wo_cap, h) ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+  return upload(g->d_wo, h) ? SRSRAN_SUCCESS : SRSRAN_ERROR;
 }
 
 // srsran_ofdm_set_freq_shift's shift_buffer (ofdm.c:432-443): per symbol, t over its cyclic prefix and body,
@@ -208,7 +184,7 @@ int build_shift(OfdmGpu* g, float f)
       h[n++]        = make_float2(cosf(y), sinf(y));
     }
   }
-  return upload(&g->d_shift, &g->shift_cap, h) ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+  return upload(g->d_shift, h) ? SRSRAN_SUCCESS : SRSRAN_ERROR;
 }
 
 // srsran_ofdm_set_phase_compensation's phasors (ofdm.c:380-406): symbol l starts at t = (samples up to the end of
@@ -228,7 +204,7 @@ int build_phase(OfdmGpu* g, double f)
     h[2 * a.nsymb + l] = make_float2(c, sn);
     count += a.N;
   }
-  return upload(&g->d_ph, &g->ph_cap, h) ? SRSRAN_SUCCESS : SRSRAN_ERROR;
+  return upload(g->d_ph, h) ? SRSRAN_SUCCESS : SRSRAN_ERROR;
 }
 
 // the option tables of the current size (configure, srsran_ofdm_set_*)
@@ -313,7 +289,7 @@ int run(srsran_ofdm_t* q, const float2* d_in, float2* d_out, uint32_t nrx, uint3
   const bool used_cfo = a.cfo_tab != nullptr;
   if (shift && g->shift_on) {  // srsran_ofdm_rx_sf's input product by shift_buffer (ofdm.c:553-555)
     if (a.cfo_tab) {         // after the CFO correction: one table, their product
-      if (!grow((void**)&g->d_comb, &g->comb_cap, a.sf_len * sizeof(float2)) ||
+      if (!g->d_comb.reserve(a.sf_len) ||
           cfo_launch(a.cfo_tab, g->d_comb, g->d_shift, a.sf_len, s) != hipSuccess) {
         return SRSRAN_ERROR;
       }
@@ -440,12 +416,6 @@ void srsran_ofdm_rx_free(srsran_ofdm_t* q)
       hipStreamSynchronize(g->stream);
       hipStreamDestroy(g->stream);
     }
-    hipFree(g->d_in);
-    hipFree(g->d_out);
-    hipFree(g->d_wo);
-    hipFree(g->d_ph);
-    hipFree(g->d_shift);
-    hipFree(g->d_comb);
     cfo_table_free(g->cfo);
     delete g;
   }
@@ -504,7 +474,7 @@ void srsran_ofdm_rx_sf_ng(srsran_ofdm_t* q, cf_t* input, cf_t* output)
     return;
   }
   const size_t ni = q->sf_sz, no = 2 * q->nof_symbols * (size_t)q->nof_re;
-  if (!grow((void**)&g->d_in, &g->in_cap, ni * sizeof(cf_t)) || !grow((void**)&g->d_out, &g->out_cap, no * sizeof(cf_t))) {
+  if (!g->d_in.reserve(ni) || !g->d_out.reserve(no)) {
     return;
   }
   hipMemcpyAsync(g->d_in, input, ni * sizeof(cf_t), hipMemcpyHostToDevice, g->stream);
@@ -555,8 +525,7 @@ int srsran_ofdm_rx_gpu_sc16(srsran_ofdm_t* q, const int16_t* d_in, float scale, 
 // ---------------- cfo.c ----------------
 struct CfoGpu {
   hipStream_t stream = nullptr;
-  float2*     d      = nullptr;
-  size_t      cap    = 0;
+  DevBuf<float2> d;
   CfoTab      tab;
 };
 
@@ -574,7 +543,7 @@ int srsran_cfo_init(srsran_cfo_t* h, uint32_t nsamples)
   CfoGpu* g = new CfoGpu();
   h->gpu    = g;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
-      !grow((void**)&g->d, &g->cap, 2 * (size_t)(nsamples ? nsamples : 1) * sizeof(float2))) {
+      !g->d.reserve(2 * (size_t)(nsamples ? nsamples : 1))) {
     srsran_cfo_free(h);
     return SRSRAN_ERROR;
   }
@@ -595,7 +564,6 @@ void srsran_cfo_free(srsran_cfo_t* h)
       hipStreamSynchronize(g->stream);
       hipStreamDestroy(g->stream);
     }
-    hipFree(g->d);
     cfo_table_free(g->tab);
     delete g;
   }
@@ -675,11 +643,11 @@ void srsran_ofdm_tx_sf(srsran_ofdm_t* q)
   }
   OfdmGpu*     g  = (OfdmGpu*)q->gpu;
   const size_t ni = 2 * q->nof_symbols * (size_t)q->nof_re, no = q->sf_sz;
-  if (!grow((void**)&g->d_in, &g->in_cap, ni * sizeof(cf_t)) || !grow((void**)&g->d_out, &g->out_cap, no * sizeof(cf_t))) {
+  if (!g->d_in.reserve(ni) || !g->d_out.reserve(no)) {
     return;
   }
   hipMemcpyAsync(g->d_in, q->cfg.in_buffer, ni * sizeof(cf_t), hipMemcpyHostToDevice, g->stream);
-  if (srsran_ofdm_tx_gpu(q, (const cf_t*)g->d_in, (cf_t*)g->d_out, 1, 1, 1.0f, g->stream) == SRSRAN_SUCCESS) {
+  if (srsran_ofdm_tx_gpu(q, (const cf_t*)g->d_in.get(), (cf_t*)g->d_out.get(), 1, 1, 1.0f, g->stream) == SRSRAN_SUCCESS) {
     hipMemcpyAsync(q->cfg.out_buffer, g->d_out, no * sizeof(cf_t), hipMemcpyDeviceToHost, g->stream);
   }
   hipStreamSynchronize(g->stream);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/srsran_pbch.h"
+#include "dev_buf.h"
 #include "pbch_kernel.h"
 #include "pdsch_internal.h"
 
@@ -46,27 +47,25 @@ constexpr uint32_t kSeqWords = 4 * kMaxBits / 32;
 
 struct PbchGpu {
   hipStream_t stream  = nullptr;
-  uint32_t*   d_re    = nullptr;  // PBCH_MAX_SYM
-  uint32_t*   d_seq   = nullptr;  // kSeqWords
-  float*      d_hist  = nullptr;  // 4 x kMaxBits
-  float*      d_try   = nullptr;  // PBCH_NANT_HYP x kMaxBits
-  PbchHypOut* d_hyp   = nullptr;  // PBCH_HYP
-  PbchState*  d_state = nullptr;
+  DevBuf<uint32_t>   d_re;     // PBCH_MAX_SYM
+  DevBuf<uint32_t>   d_seq;    // kSeqWords
+  DevBuf<float>      d_hist;   // 4 x kMaxBits
+  DevBuf<float>      d_try;    // PBCH_NANT_HYP x kMaxBits
+  DevBuf<PbchHypOut> d_hyp;    // PBCH_HYP
+  DevBuf<PbchState>  d_state;
   bool        ready   = false;  // a cell is set
   // host-synchronous calls: slot 1's first four symbols of the grid and of every port's estimate, noise, result
-  float2*  d_grid  = nullptr;  // 4 x kMaxNre
-  float2*  d_ce    = nullptr;  // 4 ports x 4 x kMaxNre
-  float*   d_noise = nullptr;
-  PbchOut* d_out   = nullptr;
+  DevBuf<float2>  d_grid;  // 4 x kMaxNre
+  DevBuf<float2>  d_ce;    // 4 ports x 4 x kMaxNre
+  DevBuf<float>   d_noise;
+  DevBuf<PbchOut> d_out;
   // batches whose first entry is this object
-  PbchEntry*             d_entries = nullptr;
-  uint32_t               entries_cap = 0;
+  DevBuf<PbchEntry>      d_entries;
   std::vector<PbchEntry> h_entries;
   // srsran_ue_mib_gpu_decode_batch: the object's grid, estimates (rows of 12 nof_prb) and measurements
-  float2* d_mib_grid = nullptr;
-  float2* d_mib_ce   = nullptr;
-  float*  d_mib_res  = nullptr;
-  uint32_t* d_mib_sf = nullptr;  // the subframe index the batch estimator reads: 0
+  DevBuf<float2>   d_mib_grid, d_mib_ce;
+  DevBuf<float>    d_mib_res;
+  DevBuf<uint32_t> d_mib_sf;  // the subframe index the batch estimator reads: 0
 };
 
 // srsran_sequence_LTE_pr (sequence.c, 36.211 7.2): len bits of the Gold sequence of c_init, packed
@@ -93,21 +92,6 @@ void pbch_free_gpu(PbchGpu* g)
   if (g->stream) {
     hipStreamDestroy(g->stream);
   }
-  hipFree(g->d_re);
-  hipFree(g->d_seq);
-  hipFree(g->d_hist);
-  hipFree(g->d_try);
-  hipFree(g->d_hyp);
-  hipFree(g->d_state);
-  hipFree(g->d_grid);
-  hipFree(g->d_ce);
-  hipFree(g->d_noise);
-  hipFree(g->d_out);
-  hipFree(g->d_entries);
-  hipFree(g->d_mib_grid);
-  hipFree(g->d_mib_ce);
-  hipFree(g->d_mib_res);
-  hipFree(g->d_mib_sf);
   delete g;
 }
 
@@ -140,14 +124,11 @@ PbchEntry object_entry(const srsran_pbch_t* q, bool mib_rule)
 int enqueue(PbchGpu* owner, PbchOut* d_out, hipStream_t st)
 {
   const uint32_t n = (uint32_t)owner->h_entries.size();
-  if (n > owner->entries_cap) {
+  if (n > owner->d_entries.cap()) {
     hipDeviceSynchronize();  // an earlier batch on another stream may still read the descriptors
-    hipFree(owner->d_entries);
-    owner->d_entries = nullptr, owner->entries_cap = 0;
-    if (hipMalloc((void**)&owner->d_entries, n * sizeof(PbchEntry)) != hipSuccess) {
+    if (!owner->d_entries.reserve(n)) {
       return SRSRAN_ERROR;
     }
-    owner->entries_cap = n;
   }
   // h_entries is pageable: the runtime stages such a copy before it returns, so the next batch may overwrite the
   // vector at once (phich_api.cpp relies on the same); calls that were ever to overlap on the host would need
@@ -181,10 +162,10 @@ int set_state(srsran_pbch_t* q, const uint32_t* frame_idx, const uint32_t* miss_
 {
   PbchGpu* g = (PbchGpu*)q->gpu;
   hipDeviceSynchronize();
-  if (frame_idx && hipMemcpy(&g->d_state->frame_idx, frame_idx, sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (frame_idx && hipMemcpy(&g->d_state.get()->frame_idx, frame_idx, sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
     return SRSRAN_ERROR;
   }
-  if (miss_cnt && hipMemcpy(&g->d_state->miss_cnt, miss_cnt, sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (miss_cnt && hipMemcpy(&g->d_state.get()->miss_cnt, miss_cnt, sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
     return SRSRAN_ERROR;
   }
   return SRSRAN_SUCCESS;
@@ -320,16 +301,10 @@ int srsran_pbch_init(srsran_pbch_t* q)
     return SRSRAN_ERROR;
   }
   const size_t rows = 4 * (size_t)kMaxNre;
-  if (hipMalloc((void**)&g->d_re, PBCH_MAX_SYM * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&g->d_seq, kSeqWords * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&g->d_hist, 4 * kMaxBits * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->d_try, PBCH_NANT_HYP * kMaxBits * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->d_hyp, PBCH_HYP * sizeof(PbchHypOut)) != hipSuccess ||
-      hipMalloc((void**)&g->d_state, sizeof(PbchState)) != hipSuccess ||
-      hipMalloc((void**)&g->d_grid, rows * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_ce, SRSRAN_MAX_PORTS * rows * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_noise, sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->d_out, sizeof(PbchOut)) != hipSuccess ||
+  if (!g->d_re.reserve(PBCH_MAX_SYM) || !g->d_seq.reserve(kSeqWords) || !g->d_hist.reserve(4 * kMaxBits) ||
+      !g->d_try.reserve(PBCH_NANT_HYP * kMaxBits) || !g->d_hyp.reserve(PBCH_HYP) || !g->d_state.reserve(1) ||
+      !g->d_grid.reserve(rows) || !g->d_ce.reserve(SRSRAN_MAX_PORTS * rows) || !g->d_noise.reserve(1) ||
+      !g->d_out.reserve(1) ||
       hipMemset(g->d_hist, 0, 4 * kMaxBits * sizeof(float)) != hipSuccess ||
       hipMemset(g->d_try, 0, PBCH_NANT_HYP * kMaxBits * sizeof(float)) != hipSuccess ||
       hipMemset(g->d_hyp, 0, PBCH_HYP * sizeof(PbchHypOut)) != hipSuccess ||
@@ -543,10 +518,9 @@ int srsran_ue_mib_init(srsran_ue_mib_t* q, cf_t* in_buffer, uint32_t max_prb)
   cfg.sf_type    = SRSRAN_SF_NORM;
   if (!q->sf_symbols || srsran_ofdm_rx_init_cfg(&q->fft, &cfg) || srsran_chest_dl_init(&q->chest, max_prb, 1) ||
       srsran_chest_dl_res_init(&q->chest_res, max_prb) ||
-      hipMalloc((void**)&g->d_mib_grid, (size_t)SRSRAN_SF_LEN_RE(max_prb, SRSRAN_CP_NORM) * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_mib_ce, SRSRAN_MAX_PORTS * (size_t)12 * max_prb * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_mib_res, 4 * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->d_mib_sf, sizeof(uint32_t)) != hipSuccess ||
+      !g->d_mib_grid.reserve((size_t)SRSRAN_SF_LEN_RE(max_prb, SRSRAN_CP_NORM)) ||
+      !g->d_mib_ce.reserve(SRSRAN_MAX_PORTS * (size_t)12 * max_prb) || !g->d_mib_res.reserve(4) ||
+      !g->d_mib_sf.reserve(1) ||
       hipMemset(g->d_mib_sf, 0, sizeof(uint32_t)) != hipSuccess) {
     srsran_ue_mib_free(q);
     return SRSRAN_ERROR;
@@ -628,9 +602,9 @@ int srsran_ue_mib_gpu_decode_batch(uint32_t nof_entries, const srsran_ue_mib_gpu
     srsran_ue_mib_t* m   = entries[i].q;
     PbchGpu*         g   = (PbchGpu*)m->pbch.gpu;
     const uint32_t   nre = 12 * m->pbch.cell.nof_prb;
-    if (srsran_ofdm_rx_gpu(&m->fft, entries[i].d_samples, (cf_t*)g->d_mib_grid, 1, 1, 0.0f, stream) ||
-        srsran_chest_dl_gpu_estimate_batch_cfg(&m->chest, &chest_cfg, g->d_mib_sf, 1, (const cf_t*)g->d_mib_grid, 0,
-                                               (cf_t*)g->d_mib_ce, 0, 0, g->d_mib_res, stream)) {
+    if (srsran_ofdm_rx_gpu(&m->fft, entries[i].d_samples, (cf_t*)g->d_mib_grid.get(), 1, 1, 0.0f, stream) ||
+        srsran_chest_dl_gpu_estimate_batch_cfg(&m->chest, &chest_cfg, g->d_mib_sf, 1, (const cf_t*)g->d_mib_grid.get(), 0,
+                                               (cf_t*)g->d_mib_ce.get(), 0, 0, g->d_mib_res, stream)) {
       return SRSRAN_ERROR;
     }
     PbchEntry e = object_entry(&m->pbch, true);

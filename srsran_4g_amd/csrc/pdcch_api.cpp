@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/srsran_pdcch.h"
+#include "dev_buf.h"
 #include "eq_kernel.h"
 #include "pdcch_kernel.h"
 
@@ -225,21 +226,20 @@ int build_regs(srsran_regs_t* h, uint32_t phich_mi, bool mbsfn_or_sf1_6)
 // ---------------- device state ----------------
 struct CtrlGpu {
   hipStream_t  stream   = nullptr;
-  float2*      d_grid   = nullptr;  // nrx x rows x nre
-  float2*      d_ce     = nullptr;  // ports x nrx x rows x nre
-  float2*      d_x      = nullptr;  // equalised symbols (codeword order)
-  float*       d_csi    = nullptr;  // predecoder CSI scratch (1-port MMSE)
-  uint32_t*    d_idx    = nullptr;  // PCFICH: 16; PDCCH: 3 tables
+  DevBuf<float2>   d_grid;  // nrx x rows x nre
+  DevBuf<float2>   d_ce;    // ports x nrx x rows x nre
+  DevBuf<float2>   d_x;     // equalised symbols (codeword order)
+  DevBuf<float>    d_csi;   // predecoder CSI scratch (1-port MMSE)
+  DevBuf<uint32_t> d_idx;   // PCFICH: 16; PDCCH: 3 tables
   uint32_t     idx_off[3] = {0, 0, 0};
-  uint32_t*    d_seq    = nullptr;  // 10 subframes x seq_words
+  DevBuf<uint32_t> d_seq;   // 10 subframes x seq_words
   uint32_t     seq_words = 0;
-  float*       d_llr    = nullptr;  // PDCCH: 72 * max_cce; PCFICH: data_f
-  uint32_t*    d_cfi    = nullptr;
-  float*       d_corr   = nullptr;
-  PdcchCand*   d_cand   = nullptr;
-  PdcchCandOut* d_out   = nullptr;
-  PdcchCandOut* h_out   = nullptr;  // pinned
-  uint32_t     cand_cap = 0;
+  DevBuf<float>    d_llr;   // PDCCH: 72 * max_cce; PCFICH: data_f
+  DevBuf<uint32_t> d_cfi;
+  DevBuf<float>    d_corr;
+  DevBuf<PdcchCand>    d_cand;
+  DevBuf<PdcchCandOut> d_out;
+  PinBuf<PdcchCandOut> h_out;  // pinned
   uint32_t     rows = 0, nre = 0, nrx = 0, ports = 0;
 };
 
@@ -252,18 +252,6 @@ void ctrl_free(CtrlGpu* g)
     hipStreamSynchronize(g->stream);
     hipStreamDestroy(g->stream);
   }
-  hipFree(g->d_grid);
-  hipFree(g->d_ce);
-  hipFree(g->d_x);
-  hipFree(g->d_csi);
-  hipFree(g->d_idx);
-  hipFree(g->d_seq);
-  hipFree(g->d_llr);
-  hipFree(g->d_cfi);
-  hipFree(g->d_corr);
-  hipFree(g->d_cand);
-  hipFree(g->d_out);
-  hipHostFree(g->h_out);
   delete g;
 }
 
@@ -273,15 +261,10 @@ CtrlGpu* ctrl_new(uint32_t max_prb, uint32_t nof_rx)
   const size_t nre = 12 * (size_t)max_prb;
   g->nrx       = nof_rx;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&g->d_grid, nof_rx * 4 * nre * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_ce, 4 * nof_rx * 4 * nre * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_x, 4 * nre * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_csi, 2 * 4 * nre * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->d_idx, (16 + 3 * 4 * nre) * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&g->d_seq, 10 * ((72 * 100 + 31) / 32) * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&g->d_llr, 72 * 100 * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->d_cfi, sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&g->d_corr, sizeof(float)) != hipSuccess) {
+      !g->d_grid.reserve(nof_rx * 4 * nre) || !g->d_ce.reserve(4 * nof_rx * 4 * nre) || !g->d_x.reserve(4 * nre) ||
+      !g->d_csi.reserve(2 * 4 * nre) || !g->d_idx.reserve(16 + 3 * 4 * nre) ||
+      !g->d_seq.reserve(10 * ((72 * 100 + 31) / 32)) || !g->d_llr.reserve(72 * 100) || !g->d_cfi.reserve(1) ||
+      !g->d_corr.reserve(1)) {
     ctrl_free(g);
     return nullptr;
   }
@@ -663,17 +646,8 @@ int srsran_pdcch_gpu_decode_msgs(srsran_pdcch_t* q, srsran_dl_sf_cfg_t* sf, srsr
     }
     c[i] = {m.location.L, m.location.ncce, nb};
   }
-  if (nof_msg > g->cand_cap) {
-    hipFree(g->d_cand);
-    hipFree(g->d_out);
-    hipHostFree(g->h_out);
-    g->d_cand = nullptr, g->d_out = nullptr, g->h_out = nullptr, g->cand_cap = 0;
-    if (hipMalloc((void**)&g->d_cand, nof_msg * sizeof(PdcchCand)) != hipSuccess ||
-        hipMalloc((void**)&g->d_out, nof_msg * sizeof(PdcchCandOut)) != hipSuccess ||
-        hipHostMalloc((void**)&g->h_out, nof_msg * sizeof(PdcchCandOut)) != hipSuccess) {
-      return SRSRAN_ERROR;
-    }
-    g->cand_cap = nof_msg;
+  if (!g->d_cand.reserve(nof_msg) || !g->d_out.reserve(nof_msg) || !g->h_out.reserve(nof_msg)) {
+    return SRSRAN_ERROR;
   }
   if (hipMemcpyAsync(g->d_cand, c.data(), nof_msg * sizeof(PdcchCand), hipMemcpyHostToDevice, g->stream) !=
           hipSuccess ||

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/srsran_pdcch.h"
+#include "dev_buf.h"
 #include "llr_kernel.h"
 #include "pdsch_internal.h"
 #include "stage_copy.h"
@@ -33,10 +34,14 @@ namespace {
 
 constexpr uint32_t kMaxQm = 8;
 
-struct Table {
+struct Table {                 // what a batch holds of a cached table (the cache owns the memory)
   uint32_t* d      = nullptr;  // len RE entries, then npairs CSI pairs (PredArgs::pairs)
   uint32_t  len    = 0;
   uint32_t  npairs = 0;
+};
+struct CachedTable {
+  DevBuf<uint32_t> buf;
+  Table            view;
 };
 
 using TableKey = std::array<uint64_t, 5>;  // RE table cache key (get_table)
@@ -53,8 +58,7 @@ struct StageSlot {
   bool       used   = false;
   char*      h      = nullptr;  // pinned coherent host memory (stage_host_alloc)
   char*      hd     = nullptr;  // its device alias
-  char*      d      = nullptr;
-  size_t     cap    = 0;
+  DevBuf<char> d;               // same capacity
 };
 
 struct PdschGpu {
@@ -64,11 +68,9 @@ struct PdschGpu {
   uint32_t                     ring_next = 0;
   srsran_amd::StageFence       fence;  // the copy kernel's "slot read" words (stage_copy.h)
   srsran_amd::StreamHandoff    ho;     // stream of the previous batch (device-side reuse of slots and d_work)
-  char*                        d_work    = nullptr;
-  size_t                       work_cap  = 0;
-  float2*                      d_in      = nullptr;  // host-synchronous path: grids + estimates
-  size_t                       in_cap    = 0;
-  std::map<TableKey, Table>    tables;
+  DevBuf<char>                 d_work;
+  DevBuf<float2>               d_in;  // host-synchronous path: grids + estimates
+  std::map<TableKey, CachedTable> tables;
   struct LlrRef {
     uint32_t       sf, tb, n;
     const int16_t* d;
@@ -82,28 +84,20 @@ struct PdschGpu {
   uint32_t            evm_max_bits = 0;  // srsran_evm_buffer_t.max_bits (pdsch.c:297, 468-471)
 };
 
-bool grow_dev(void** p, size_t* cap, size_t need)
+// 64 KB floor; the device is idle before a block that enqueued work may still use is released
+template <typename T>
+bool reserve_idle(DevBuf<T>& b, size_t bytes)
 {
-  if (*cap >= need) {
-    return true;
+  const size_t n = (bytes + sizeof(T) - 1) / sizeof(T);
+  if (n > b.cap() && b.get()) {
+    hipDeviceSynchronize();
   }
-  if (*p) {
-    hipDeviceSynchronize();  // buffers may still be in use by enqueued work
-    hipFree(*p);
-  }
-  *p   = nullptr;
-  *cap = 0;
-  need = std::max(need, (size_t)65536);
-  if (hipMalloc(p, need) != hipSuccess) {
-    return false;
-  }
-  *cap = need;
-  return true;
+  return b.reserve(n, 65536 / sizeof(T));
 }
 
 bool grow_stage(PdschGpu* g, StageSlot& st, size_t need)
 {
-  if (st.cap >= need) {
+  if (st.d.cap() >= need) {
     return true;
   }
   if (st.used) {  // the slot's last batch is done with both copies
@@ -113,18 +107,11 @@ bool grow_stage(PdschGpu* g, StageSlot& st, size_t need)
       srsran_amd::handoff_drain(g->ho);
     }
   }
-  hipHostFree(st.h);
-  hipFree(st.d);
-  st.h   = nullptr;
-  st.d   = nullptr;
-  st.cap = 0;
-  need   = std::max(need, (size_t)65536);
+  hipHostFree(st.h);  // stage_host_alloc's memory (stage_copy.h)
+  st.d.reset();
+  need = std::max(need, (size_t)65536);
   st.h = (char*)srsran_amd::stage_host_alloc(need, (void**)&st.hd);
-  if (!st.h || hipMalloc((void**)&st.d, need) != hipSuccess) {
-    return false;
-  }
-  st.cap = need;
-  return true;
+  return st.h && st.d.reserve(need);
 }
 
 bool init_ring(PdschGpu* g)
@@ -148,9 +135,6 @@ void table_evict(PdschGpu* g, uint32_t nsf)
 {
   if (g->tables.size() + nsf > kTableCache) {
     hipDeviceSynchronize();
-    for (auto& kv : g->tables) {
-      hipFree(kv.second.d);
-    }
     g->tables.clear();
   }
 }
@@ -171,7 +155,7 @@ Table get_table(srsran_pdsch_t* q, PdschGpu* g, const srsran_pdsch_grant_t& gr, 
            (uint64_t)sf_idx << 24;
   auto it = g->tables.find(key);
   if (it != g->tables.end()) {
-    return it->second;
+    return it->second.view;
   }
   std::vector<uint32_t> t = pdsch_re_table(q->cell, gr, lstart, sf_idx);
   Table                 tb;
@@ -191,12 +175,15 @@ Table get_table(srsran_pdsch_t* q, PdschGpu* g, const srsran_pdsch_grant_t& gr, 
     }
   }
   tb.npairs = (uint32_t)t.size() - tb.len;
-  if (hipMalloc((void**)&tb.d, std::max<size_t>(t.size(), 1) * sizeof(uint32_t)) != hipSuccess ||
-      hipMemcpy(tb.d, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(tb.d);
+  DevBuf<uint32_t> buf;
+  if (!buf.reserve(std::max<size_t>(t.size(), 1)) ||
+      hipMemcpy(buf, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
     return Table{};
   }
-  return g->tables[key] = tb;
+  tb.d             = buf;
+  CachedTable& ct  = g->tables[key];
+  ct.buf           = std::move(buf);
+  return ct.view = tb;
 }
 
 // One decoded codeword of the batch
@@ -311,12 +298,12 @@ int enqueue_llr(srsran_pdsch_t* q, uint32_t nsf, const srsran_pdsch_gpu_sf_t* sf
   const size_t e_sz = align256((size_t)nsf * 2 * max_re * kMaxQm * sizeof(int16_t));
   const uint32_t evm_parts = (2 * max_re + LLR_BLOCK_SYMBOLS - 1) / LLR_BLOCK_SYMBOLS;  // >= blocks of any item
   const size_t   v_sz      = align256((size_t)nsf * 2 * (evm_parts + 1) * sizeof(float));
-  if (!grow_dev((void**)&g->d_work, &g->work_cap, x_sz + c_sz + m_sz + e_sz + v_sz)) {
+  if (!reserve_idle(g->d_work, x_sz + c_sz + m_sz + e_sz + v_sz)) {
     return SRSRAN_ERROR;
   }
   float* d_evm_part = (float*)(g->d_work + x_sz + c_sz + m_sz + e_sz);
   float* d_evm_out  = d_evm_part + (size_t)nsf * 2 * evm_parts;
-  float2*  d_x   = (float2*)g->d_work;
+  float2*  d_x   = (float2*)g->d_work.get();
   float*   d_csi = (float*)(g->d_work + x_sz);
   float*   d_max = (float*)(g->d_work + x_sz + c_sz);
   int16_t* d_e   = (int16_t*)(g->d_work + x_sz + c_sz + m_sz);
@@ -415,7 +402,7 @@ int enqueue_llr(srsran_pdsch_t* q, uint32_t nsf, const srsran_pdsch_gpu_sf_t* sf
     return SRSRAN_ERROR;
   }
   // every slot of the ring grows now, not when it comes round
-  if (st.cap < pa_bytes + li_bytes + ev_bytes + pp_bytes) {
+  if (st.d.cap() < pa_bytes + li_bytes + ev_bytes + pp_bytes) {
     for (StageSlot& r : g->ring) {
       if (!grow_stage(g, r, 2 * (pa_bytes + li_bytes + ev_bytes + pp_bytes))) {
         return SRSRAN_ERROR;
@@ -434,7 +421,7 @@ int enqueue_llr(srsran_pdsch_t* q, uint32_t nsf, const srsran_pdsch_gpu_sf_t* sf
     const uint32_t c = order_l[i];
     if (fused) {  // subframe c; its descriptor as uploaded: st.d + pos_of[c] PredArgs
       FusedItem& fi = hf[i];
-      fi.pa         = (const PredArgs*)st.d + pos_of[c];
+      fi.pa         = (const PredArgs*)st.d.get() + pos_of[c];
       fi.n          = pa[c].n;
       fi.csi_max    = sfs[c].cfg->csi_enable ? d_max + 2 * c : nullptr;
       for (uint32_t l = 0; l < 2; l++) {
@@ -496,7 +483,7 @@ int enqueue_llr(srsran_pdsch_t* q, uint32_t nsf, const srsran_pdsch_gpu_sf_t* sf
   if (side) {
     hipMemsetAsync(d_max, 0, (size_t)nsf * 2 * sizeof(float), s);
   }
-  const PredArgs* dp = (const PredArgs*)st.d;
+  const PredArgs* dp = (const PredArgs*)st.d.get();
   const LlrItem*  dl = (const LlrItem*)(st.d + pa_bytes);
   if (fused) {
     bool any_csi = false;
@@ -610,14 +597,8 @@ void srsran_pdsch_free(srsran_pdsch_t* q)
   PdschGpu* g = (PdschGpu*)q->gpu;
   if (g) {
     hipDeviceSynchronize();
-    for (auto& kv : g->tables) {
-      hipFree(kv.second.d);
-    }
-    hipFree(g->d_work);
-    hipFree(g->d_in);
     for (StageSlot& st : g->ring) {
-      hipFree(st.d);
-      hipHostFree(st.h);
+      hipHostFree(st.h);  // stage_host_alloc's memory (stage_copy.h)
       if (st.staged) {
         hipEventDestroy(st.staged);
       }
@@ -655,9 +636,6 @@ int srsran_pdsch_set_cell(srsran_pdsch_t* q, srsran_cell_t cell)
   }
   PdschGpu* g = (PdschGpu*)q->gpu;
   hipDeviceSynchronize();
-  for (auto& kv : g->tables) {
-    hipFree(kv.second.d);
-  }
   g->tables.clear();
   // the EVM buffer grows to the new cell (srsran_evm_buffer_resize keeps the larger of the two, pdsch.c:468-471)
   g->evm_max_bits = std::max(g->evm_max_bits,
@@ -686,7 +664,7 @@ int srsran_pdsch_decode(srsran_pdsch_t*        q,
   if (cfg->max_nof_iterations) {
     srsran_sch_set_max_noi(&q->dl_sch, cfg->max_nof_iterations);
   }
-  if (!grow_dev((void**)&g->d_in, &g->in_cap, (size_t)(nrx + np * nrx) * nsym * sizeof(float2))) {
+  if (!reserve_idle(g->d_in, (size_t)(nrx + np * nrx) * nsym * sizeof(float2))) {
     return SRSRAN_ERROR;
   }
   for (uint32_t r = 0; r < nrx; r++) {
@@ -704,7 +682,7 @@ int srsran_pdsch_decode(srsran_pdsch_t*        q,
   f.cfg     = cfg;
   f.tti     = sf->tti;
   f.cfi     = sf->cfi;
-  f.d_grid  = (const cf_t*)g->d_in;
+  f.d_grid  = (const cf_t*)g->d_in.get();
   f.d_ce    = (const cf_t*)(g->d_in + (size_t)nrx * nsym);
   f.ce_full = 1;
   f.noise   = channel->noise_estimate;
@@ -930,7 +908,7 @@ int srsran_pdsch_encode(srsran_pdsch_t*     q,
     it.mod[cw]  = (int)tb.mod;
     cw++;
   }
-  if (cw != (scheme == 3 ? 2u : scheme == 2 ? gr.nof_tb : 1u) || !grow_dev((void**)&g->d_work, &g->work_cap, off) ||
+  if (cw != (scheme == 3 ? 2u : scheme == 2 ? gr.nof_tb : 1u) || !reserve_idle(g->d_work, off) ||
       srsran_amd::handoff(g->ho, g->stream) != hipSuccess) {  // d_work: after the batches queued elsewhere
     return SRSRAN_ERROR;
   }

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "../../include/srsran_phch.h"
+#include "dev_buf.h"
 #include "devkey.h"
 #include "eq_kernel.h"
 #include "llr_kernel.h"
@@ -23,27 +24,15 @@ namespace {
 std::mutex g_mu;
 struct Ctx {  // host-synchronous stage APIs: one stream + scratch per device
   hipStream_t stream = nullptr;
-  void*       d_a    = nullptr;
-  size_t      a_cap  = 0;
-  void*       d_b    = nullptr;
-  size_t      b_cap  = 0;
+  DevBuf<uint8_t> d_a, d_b;  // bytes, 4096 floor
 };
-std::map<int, Ctx> g_ctxs;
+constexpr size_t kFloor = 4096;
 
-bool grow(void** p, size_t* cap, size_t need)
+// per-device contexts live for the process: never destroyed, so no hipFree runs after the runtime is gone
+Ctx& ctx_for(int dev)
 {
-  if (*cap >= need) {
-    return true;
-  }
-  hipFree(*p);
-  *p = nullptr;
-  need = std::max(need, (size_t)4096);
-  if (hipMalloc(p, need) != hipSuccess) {
-    *cap = 0;
-    return false;
-  }
-  *cap = need;
-  return true;
+  static auto& ctxs = *new std::map<int, Ctx>;
+  return ctxs[dev];
 }
 
 bool ctx_ready(Ctx& g_ctx)
@@ -128,14 +117,14 @@ int srsran_demod_soft_demodulate_s(srsran_mod_t modulation, const cf_t* symbols,
     return 0;
   }
   std::lock_guard<std::mutex> lk(g_mu);
-  Ctx&                        g_ctx = g_ctxs[cur_dev()];
-  if (!ctx_ready(g_ctx) || !grow(&g_ctx.d_a, &g_ctx.a_cap, (size_t)nsymbols * sizeof(cf_t)) ||
-      !grow(&g_ctx.d_b, &g_ctx.b_cap, (size_t)nsymbols * q * sizeof(int16_t))) {
+  Ctx&                        g_ctx = ctx_for(cur_dev());
+  if (!ctx_ready(g_ctx) || !g_ctx.d_a.reserve((size_t)nsymbols * sizeof(cf_t), kFloor) ||
+      !g_ctx.d_b.reserve((size_t)nsymbols * q * sizeof(int16_t), kFloor)) {
     return -1;
   }
   hipMemcpyAsync(g_ctx.d_a, symbols, (size_t)nsymbols * sizeof(cf_t), hipMemcpyHostToDevice, g_ctx.stream);
-  if (llr_launch((int)modulation, (const float*)g_ctx.d_a, (uint32_t)nsymbols, 0, 0, 0, nullptr, nullptr,
-                 (int16_t*)g_ctx.d_b, g_ctx.stream) != hipSuccess) {
+  if (llr_launch((int)modulation, (const float*)g_ctx.d_a.get(), (uint32_t)nsymbols, 0, 0, 0, nullptr, nullptr,
+                 (int16_t*)g_ctx.d_b.get(), g_ctx.stream) != hipSuccess) {
     return -1;
   }
   hipMemcpyAsync(llr, g_ctx.d_b, (size_t)nsymbols * q * sizeof(int16_t), hipMemcpyDeviceToHost, g_ctx.stream);
@@ -148,13 +137,14 @@ void srsran_sequence_apply_s(const int16_t* in, int16_t* out, uint32_t length, u
     return;
   }
   std::lock_guard<std::mutex> lk(g_mu);
-  Ctx&                        g_ctx = g_ctxs[cur_dev()];
+  Ctx&                        g_ctx = ctx_for(cur_dev());
   const size_t bytes = (size_t)length * sizeof(int16_t);
-  if (!ctx_ready(g_ctx) || !grow(&g_ctx.d_a, &g_ctx.a_cap, bytes) || !grow(&g_ctx.d_b, &g_ctx.b_cap, bytes)) {
+  if (!ctx_ready(g_ctx) || !g_ctx.d_a.reserve(bytes, kFloor) || !g_ctx.d_b.reserve(bytes, kFloor)) {
     return;
   }
   hipMemcpyAsync(g_ctx.d_a, in, bytes, hipMemcpyHostToDevice, g_ctx.stream);
-  if (seq_apply_launch((const int16_t*)g_ctx.d_a, (int16_t*)g_ctx.d_b, length, seed, g_ctx.stream) != hipSuccess) {
+  if (seq_apply_launch((const int16_t*)g_ctx.d_a.get(), (int16_t*)g_ctx.d_b.get(), length, seed, g_ctx.stream) !=
+      hipSuccess) {
     fprintf(stderr, "[srsran_sequence] launch failed\n");
     return;
   }
@@ -200,14 +190,14 @@ int srsran_predecoding_type(cf_t*              y[4],
   const size_t nin = (size_t)nof_rxant * (1 + nof_ports);  // y + h
   const size_t nout = (size_t)nof_layers;
   std::lock_guard<std::mutex> lk(g_mu);
-  Ctx&                        g_ctx = g_ctxs[cur_dev()];
-  if (!ctx_ready(g_ctx) || !grow(&g_ctx.d_a, &g_ctx.a_cap, nin * n * sizeof(cf_t)) ||
-      !grow(&g_ctx.d_b, &g_ctx.b_cap, nout * n * (sizeof(cf_t) + sizeof(float)))) {
+  Ctx&                        g_ctx = ctx_for(cur_dev());
+  if (!ctx_ready(g_ctx) || !g_ctx.d_a.reserve(nin * n * sizeof(cf_t), kFloor) ||
+      !g_ctx.d_b.reserve(nout * n * (sizeof(cf_t) + sizeof(float)), kFloor)) {
     return SRSRAN_ERROR;
   }
-  cf_t*  dy  = (cf_t*)g_ctx.d_a;
+  cf_t*  dy  = (cf_t*)g_ctx.d_a.get();
   cf_t*  dh  = dy + (size_t)nof_rxant * n;
-  cf_t*  dx  = (cf_t*)g_ctx.d_b;
+  cf_t*  dx  = (cf_t*)g_ctx.d_b.get();
   float* dcs = (float*)(dx + nout * n);
   for (int r = 0; r < nof_rxant; r++) {
     hipMemcpyAsync(dy + r * n, y[r], n * sizeof(cf_t), hipMemcpyHostToDevice, g_ctx.stream);

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/srsran_phich.h"
+#include "dev_buf.h"
 #include "phich_kernel.h"
 
 using namespace srsran_amd;
@@ -21,18 +22,16 @@ constexpr uint32_t kRows = 3;  // PHICH REs lie in symbols 0..2 (36.211 6.9.3)
 
 struct PhichGpu {
   hipStream_t stream = nullptr;
-  uint32_t*   d_re   = nullptr;  // 12 indices per mapping unit of q->regs
-  uint32_t    re_cap = 0;        // units
+  DevBuf<uint32_t> d_re;         // 12 indices per mapping unit of q->regs
   uint32_t    seq[10] = {};      // 12 scrambling bits per subframe
   // batches: items and (subframe, unit) groups on the device
-  PhichItem* d_items   = nullptr;
-  PhichUnit* d_units   = nullptr;
-  uint32_t   items_cap = 0;
+  DevBuf<PhichItem> d_items;
+  DevBuf<PhichUnit> d_units;     // same capacity
   // host-synchronous calls: control rows of the grids / estimates, noise, result
-  float2*   d_grid = nullptr;  // max(ports, rx) x kRows x nre
-  float2*   d_ce   = nullptr;  // ports x rx x kRows x nre
-  float*    d_noise = nullptr;
-  PhichOut* d_out  = nullptr;
+  DevBuf<float2>   d_grid;  // max(ports, rx) x kRows x nre
+  DevBuf<float2>   d_ce;    // ports x rx x kRows x nre
+  DevBuf<float>    d_noise;
+  DevBuf<PhichOut> d_out;
   uint32_t  nre    = 0;  // of the cell the scratch was sized for
 };
 
@@ -83,28 +82,17 @@ void phich_free_gpu(PhichGpu* g)
     hipStreamSynchronize(g->stream);
     hipStreamDestroy(g->stream);
   }
-  hipFree(g->d_re);
-  hipFree(g->d_items);
-  hipFree(g->d_units);
-  hipFree(g->d_grid);
-  hipFree(g->d_ce);
-  hipFree(g->d_noise);
-  hipFree(g->d_out);
   delete g;
 }
 
 bool upload_regs(PhichGpu* g, const srsran_regs_t* regs)
 {
   const uint32_t units = regs->ngroups_phich;
-  if (units > g->re_cap) {
+  if (12 * (size_t)units > g->d_re.cap()) {
     hipStreamSynchronize(g->stream);
-    hipFree(g->d_re);
-    g->d_re   = nullptr;
-    g->re_cap = 0;
-    if (hipMalloc((void**)&g->d_re, 12 * (size_t)units * sizeof(uint32_t)) != hipSuccess) {
+    if (!g->d_re.reserve(12 * (size_t)units)) {
       return false;
     }
-    g->re_cap = units;
   }
   return units == 0 || (hipMemcpyAsync(g->d_re, regs->phich_re, 12 * (size_t)units * sizeof(uint32_t),
                                        hipMemcpyHostToDevice, g->stream) == hipSuccess &&
@@ -140,16 +128,11 @@ int stage_items(srsran_phich_t* q, uint32_t n, const srsran_phich_gpu_item_t* it
       units->back().count++;
     }
   }
-  if (n > g->items_cap) {
+  if (n > g->d_items.cap() || n > g->d_units.cap()) {
     hipDeviceSynchronize();  // an earlier batch on another stream may still read the buffers
-    hipFree(g->d_items);
-    hipFree(g->d_units);
-    g->d_items = nullptr, g->d_units = nullptr, g->items_cap = 0;
-    if (hipMalloc((void**)&g->d_items, n * sizeof(PhichItem)) != hipSuccess ||
-        hipMalloc((void**)&g->d_units, n * sizeof(PhichUnit)) != hipSuccess) {
+    if (!g->d_items.reserve(n) || !g->d_units.reserve(n)) {
       return SRSRAN_ERROR;
     }
-    g->items_cap = n;
   }
   if (hipMemcpyAsync(g->d_items, it.data(), n * sizeof(PhichItem), hipMemcpyHostToDevice, st) != hipSuccess ||
       (units && hipMemcpyAsync(g->d_units, units->data(), units->size() * sizeof(PhichUnit), hipMemcpyHostToDevice,
@@ -168,15 +151,10 @@ bool scratch(srsran_phich_t* q)
     return true;
   }
   hipStreamSynchronize(g->stream);
-  hipFree(g->d_grid);
-  hipFree(g->d_ce);
-  hipFree(g->d_noise);
-  hipFree(g->d_out);
-  g->d_grid = nullptr, g->d_ce = nullptr, g->d_noise = nullptr, g->d_out = nullptr, g->nre = 0;
-  const size_t plane = (size_t)kRows * nre * sizeof(float2);
-  if (hipMalloc((void**)&g->d_grid, 4 * plane) != hipSuccess || hipMalloc((void**)&g->d_ce, 16 * plane) != hipSuccess ||
-      hipMalloc((void**)&g->d_noise, sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&g->d_out, sizeof(PhichOut)) != hipSuccess) {
+  g->d_grid.reset(), g->d_ce.reset();  // sized for the cell
+  g->nre             = 0;
+  const size_t plane = (size_t)kRows * nre;
+  if (!g->d_grid.reserve(4 * plane) || !g->d_ce.reserve(16 * plane) || !g->d_noise.reserve(1) || !g->d_out.reserve(1)) {
     return false;
   }
   g->nre = nre;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/srsran_prach.h"
+#include "dev_buf.h"
 #include "prach_kernel.h"
 
 using namespace srsran_amd;
@@ -38,23 +39,22 @@ struct Metrics {
 struct PrachGpu {
   hipStream_t stream = nullptr;
   // per configuration
-  float2*  d_tw_n   = nullptr;  // N
-  float2*  d_tw_m   = nullptr;  // 12 N
-  float2*  d_tw839  = nullptr;  // exp(+2 pi i m / 839)
-  float2*  d_seqs   = nullptr;  // [64][839]
-  float2*  d_spec   = nullptr;  // [64][839]
+  DevBuf<float2> d_tw_n;    // N
+  DevBuf<float2> d_tw_m;    // 12 N
+  DevBuf<float2> d_tw839;   // exp(+2 pi i m / 839)
+  DevBuf<float2> d_seqs;    // [64][839]
+  DevBuf<float2> d_spec;    // [64][839]
   uint32_t tw_N     = 0;        // the size d_tw_n / d_tw_m were built for
   OfdmArgs fft      = {};  // only the plan is set (prach_kernel.h)
   // host-synchronous calls
-  float2* d_sig = nullptr;  // 12 max_N (detect input)
-  float2* d_gen = nullptr;  // SRSRAN_PRACH_MAX_LEN scaled to max_N (gen output)
-  // batch workspace (of the batch's first object)
-  uint32_t     cap    = 0;
-  PrachOcc*    h_occ  = nullptr;  // pinned
-  PrachOcc*    d_occ  = nullptr;
-  PrachOccOut* h_out  = nullptr;  // pinned
-  PrachOccOut* d_out  = nullptr;
-  float2*      d_part = nullptr;  // [cap][12][839]
+  DevBuf<float2> d_sig;  // 12 max_N (detect input)
+  DevBuf<float2> d_gen;  // SRSRAN_PRACH_MAX_LEN scaled to max_N (gen output)
+  // batch workspace (of the batch's first object): all five for the same number of occasions, d_occ.cap()
+  PinBuf<PrachOcc>    h_occ;
+  DevBuf<PrachOcc>    d_occ;
+  PinBuf<PrachOccOut> h_out;
+  DevBuf<PrachOccOut> d_out;
+  DevBuf<float2>      d_part;  // [occasions][12][839]
   Metrics      metrics;
   // srsran_prach_gpu_detect_time: events around the two kernels of a detect run on this object's stream
   bool       timing = false;
@@ -64,20 +64,12 @@ struct PrachGpu {
 
 void release_batch(PrachGpu* g)
 {
-  hipHostFree(g->h_occ);
-  hipHostFree(g->h_out);
-  hipFree(g->d_occ);
-  hipFree(g->d_out);
-  hipFree(g->d_part);
-  g->h_occ = g->d_occ = nullptr;
-  g->h_out = g->d_out = nullptr;
-  g->d_part           = nullptr;
-  g->cap              = 0;
+  g->h_occ.reset(), g->h_out.reset(), g->d_occ.reset(), g->d_out.reset(), g->d_part.reset();
 }
 
 bool reserve(PrachGpu* g, uint32_t n)
 {
-  if (n <= g->cap) {
+  if (n <= g->d_occ.cap()) {
     return true;
   }
   hipStreamSynchronize(g->stream);
@@ -86,15 +78,11 @@ bool reserve(PrachGpu* g, uint32_t n)
   while (m < n) {
     m *= 2;
   }
-  if (hipHostMalloc((void**)&g->h_occ, m * sizeof(PrachOcc)) != hipSuccess ||
-      hipHostMalloc((void**)&g->h_out, m * sizeof(PrachOccOut)) != hipSuccess ||
-      hipMalloc((void**)&g->d_occ, m * sizeof(PrachOcc)) != hipSuccess ||
-      hipMalloc((void**)&g->d_out, m * sizeof(PrachOccOut)) != hipSuccess ||
-      hipMalloc((void**)&g->d_part, (size_t)m * PRACH_K * PRACH_NZC * sizeof(float2)) != hipSuccess) {
+  if (!g->h_occ.reserve(m) || !g->h_out.reserve(m) || !g->d_occ.reserve(m) || !g->d_out.reserve(m) ||
+      !g->d_part.reserve((size_t)m * PRACH_K * PRACH_NZC)) {
     release_batch(g);
     return false;
   }
-  g->cap = m;
   return true;
 }
 
@@ -376,13 +364,10 @@ int srsran_prach_init(srsran_prach_t* p, uint32_t max_N_ifft_ul)
   // the longest preamble (formats 2 / 3: 2 x 24576 + 21024 T_s) at this symbol size
   const size_t gen_len = (size_t)SRSRAN_PRACH_MAX_LEN * max_N_ifft_ul / 2048 + 1;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&g->d_tw_n, max_N_ifft_ul * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_tw_m, (size_t)PRACH_K * max_N_ifft_ul * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_tw839, PRACH_NZC * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_seqs, N_SEQS * PRACH_NZC * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_spec, N_SEQS * PRACH_NZC * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_sig, (size_t)PRACH_K * max_N_ifft_ul * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_gen, gen_len * sizeof(float2)) != hipSuccess || !reserve(g, 16)) {
+      !g->d_tw_n.reserve(max_N_ifft_ul) || !g->d_tw_m.reserve((size_t)PRACH_K * max_N_ifft_ul) ||
+      !g->d_tw839.reserve(PRACH_NZC) || !g->d_seqs.reserve(N_SEQS * PRACH_NZC) ||
+      !g->d_spec.reserve(N_SEQS * PRACH_NZC) || !g->d_sig.reserve((size_t)PRACH_K * max_N_ifft_ul) ||
+      !g->d_gen.reserve(gen_len) || !reserve(g, 16)) {
     srsran_prach_free(p);
     return SRSRAN_ERROR;
   }
@@ -552,7 +537,7 @@ int srsran_prach_detect_offset(srsran_prach_t* p,
       hipSuccess) {
     return SRSRAN_ERROR;
   }
-  srsran_prach_gpu_occ_t occ = {p, freq_offset, (const cf_t*)g->d_sig, sig_len};
+  srsran_prach_gpu_occ_t occ = {p, freq_offset, (const cf_t*)g->d_sig.get(), sig_len};
   static thread_local srsran_prach_gpu_res_t res;
   if (detect_core(1, &occ, &b0, &res) != SRSRAN_SUCCESS) {
     return SRSRAN_ERROR;
@@ -636,20 +621,12 @@ int srsran_prach_free(srsran_prach_t* p)
     if (g->stream) {
       hipStreamSynchronize(g->stream);
     }
-    release_batch(g);
     if (g->ev0) {
       hipEventDestroy(g->ev0);
     }
     if (g->ev1) {
       hipEventDestroy(g->ev1);
     }
-    hipFree(g->d_tw_n);
-    hipFree(g->d_tw_m);
-    hipFree(g->d_tw839);
-    hipFree(g->d_seqs);
-    hipFree(g->d_spec);
-    hipFree(g->d_sig);
-    hipFree(g->d_gen);
     if (g->stream) {
       hipStreamDestroy(g->stream);
     }

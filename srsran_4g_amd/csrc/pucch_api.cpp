@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/srsran_pucch.h"
+#include "dev_buf.h"
 #include "pucch_kernel.h"
 #include "pucch_tx_kernel.h"
 
@@ -389,35 +390,23 @@ ChestScalars chest_scalars(const PucchCandOut& o)
 // ---------------- device state of srsran_pucch_t ----------------
 struct PucchGpu {
   hipStream_t   stream = nullptr;
-  PucchCand*    h_cand = nullptr;  // pinned
-  PucchCandOut* h_out  = nullptr;  // pinned
-  PucchCand*    d_cand = nullptr;
-  PucchCandOut* d_out  = nullptr;
-  uint32_t      cap    = 0;        // candidates
-  float2*       d_re   = nullptr;  // srsran_pucch_decode: gathered data REs and estimates; srsran_pucch_encode: z
-  PucchTxUe*    d_tx   = nullptr;  // srsran_pucch_encode: the descriptor (allocated by the first call)
+  PinBuf<PucchCand>    h_cand;  // the four candidate buffers have one capacity (reserve below), d_out.cap()
+  PinBuf<PucchCandOut> h_out;
+  DevBuf<PucchCand>    d_cand;
+  DevBuf<PucchCandOut> d_out;
+  DevBuf<float2>       d_re;  // srsran_pucch_decode: gathered data REs and estimates; srsran_pucch_encode: z
+  DevBuf<PucchTxUe>    d_tx;  // srsran_pucch_encode: the descriptor (allocated by the first call)
 };
 
 bool reserve(PucchGpu* g, uint32_t n)
 {
-  if (n <= g->cap) {
+  if (n <= g->d_out.cap()) {
     return true;
   }
   hipStreamSynchronize(g->stream);
-  hipHostFree(g->h_cand);
-  hipHostFree(g->h_out);
-  hipFree(g->d_cand);
-  hipFree(g->d_out);
-  g->h_cand = nullptr, g->h_out = nullptr, g->d_cand = nullptr, g->d_out = nullptr, g->cap = 0;
+  g->h_cand.reset(), g->h_out.reset(), g->d_cand.reset(), g->d_out.reset();
   const uint32_t m = std::max<uint32_t>(64, n + n / 2);
-  if (hipHostMalloc((void**)&g->h_cand, m * sizeof(PucchCand)) != hipSuccess ||
-      hipHostMalloc((void**)&g->h_out, m * sizeof(PucchCandOut)) != hipSuccess ||
-      hipMalloc((void**)&g->d_cand, m * sizeof(PucchCand)) != hipSuccess ||
-      hipMalloc((void**)&g->d_out, m * sizeof(PucchCandOut)) != hipSuccess) {
-    return false;
-  }
-  g->cap = m;
-  return true;
+  return g->h_cand.reserve(m) && g->h_out.reserve(m) && g->d_cand.reserve(m) && g->d_out.reserve(m);
 }
 
 // one pass of get_pucch (enb_ul.c:156-231) planned on the host: format and candidate resources
@@ -902,7 +891,7 @@ int srsran_pucch_init_enb(srsran_pucch_t* q)
   PucchGpu* g = new PucchGpu();
   q->gpu      = g;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess || !reserve(g, 64) ||
-      hipMalloc((void**)&g->d_re, 2 * PUCCH_MAX_RE * sizeof(float2)) != hipSuccess) {
+      !g->d_re.reserve(2 * PUCCH_MAX_RE)) {
     srsran_pucch_free(q);
     return SRSRAN_ERROR;
   }
@@ -920,12 +909,6 @@ void srsran_pucch_free(srsran_pucch_t* q)
       hipStreamSynchronize(g->stream);
       hipStreamDestroy(g->stream);
     }
-    hipHostFree(g->h_cand);
-    hipHostFree(g->h_out);
-    hipFree(g->d_cand);
-    hipFree(g->d_out);
-    hipFree(g->d_re);
-    hipFree(g->d_tx);
     delete g;
   }
   memset(q, 0, sizeof(*q));
@@ -1339,8 +1322,7 @@ int srsran_pucch_encode(srsran_pucch_t*     q,
     fprintf(stderr, "[srsran_pucch] Error encoding PUCCH (format %s)\n", srsran_pucch_format_text(cfg->format));
     return SRSRAN_ERROR;
   }
-  if (!g->d_tx && hipMalloc((void**)&g->d_tx, sizeof(PucchTxUe)) != hipSuccess) {
-    g->d_tx = nullptr;
+  if (!g->d_tx.reserve(1)) {
     return SRSRAN_ERROR;
   }
   const uint32_t nre = (d.n_sf[0] + d.n_sf[1]) * SRSRAN_NRE;

@@ -15,6 +15,7 @@
 
 #include "../../include/srsran_pusch.h"
 #include "../../include/srsran_ue_ul.h"
+#include "dev_buf.h"
 #include "llr_kernel.h"
 #include "ofdm_kernel.h"
 #include "pusch_kernel.h"
@@ -173,39 +174,21 @@ bool dft_plan(uint32_t M, PuschUe& u)
   return n == 1;
 }
 
-bool grow(void** p, size_t* cap, size_t need)
-{
-  if (need <= *cap) {
-    return true;
-  }
-  hipFree(*p);
-  *p   = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, need) != hipSuccess) {
-    return false;
-  }
-  *cap = need;
-  return true;
-}
-
 // ---------------- chest_ul device state ----------------
 struct ChestUlGpu {
   hipStream_t         stream = nullptr;
   uint32_t            max_prb = 0;
   UlHopping           hop;
   bool                hop_ok = false;
-  float2*             d_dmrs = nullptr;  // [cs][sf][valid n <= cell prb] 2 * 12 n values
-  size_t              dmrs_cap = 0;
-  std::vector<size_t> dmrs_off;          // (cs * 10 + sf) * 101 + n -> offset (values)
-  float2*             d_grid = nullptr;  // one subframe grid
-  size_t              grid_cap = 0;
-  PuschUe*            d_desc = nullptr;
-  size_t              desc_cap = 0;
+  DevBuf<float2>      d_dmrs;    // [cs][sf][valid n <= cell prb] 2 * 12 n values
+  std::vector<size_t> dmrs_off;  // (cs * 10 + sf) * 101 + n -> offset (values)
+  DevBuf<float2>      d_grid;    // one subframe grid
+  DevBuf<PuschUe>     d_desc;
 };
 
 struct ChestUlResGpu {
-  float2*     d_ce  = nullptr;  // nof_re values
-  ChestUlOut* d_out = nullptr;
+  DevBuf<float2>     d_ce;  // nof_re values
+  DevBuf<ChestUlOut> d_out;
   uint32_t    nof_re = 0;
   bool        valid  = false;   // d_ce holds the last estimate written to ce
 };
@@ -284,32 +267,20 @@ int check_alloc(const srsran_cell_t& cell, const srsran_pusch_cfg_t* cfg)
 
 // ---------------- PUSCH device state ----------------
 struct PuschGpu {
-  float2*     d_grid = nullptr;  // subframe grid (sync API)
-  float2*     d_ce   = nullptr;  // estimate grid uploaded from the host (sync API, channel->gpu absent)
-  size_t      grid_cap = 0, ce_cap = 0;
-  float2*     d_sym  = nullptr;  // de-precoded symbols
-  size_t      sym_cap = 0;
-  int16_t*    d_q    = nullptr;  // LLRs
-  size_t      q_cap  = 0;
-  uint8_t*    d_c    = nullptr;  // unpacked scrambling sequence
-  size_t      c_cap  = 0;
-  PuschUe*    d_desc = nullptr;
-  size_t      desc_cap = 0;
-  LlrItem*    d_llr  = nullptr;
-  size_t      llr_cap = 0;
-  ChestUlOut* d_out  = nullptr;  // per-UE outputs (sync API: one; batch: nof_ue)
-  size_t      out_cap = 0;
-  float2*     d_bce  = nullptr;  // batch: per-UE estimate grids
-  size_t      bce_cap = 0;
-  int16_t*    d_g    = nullptr;  // batch: de-interleaved LLRs of the UEs without UCI
-  size_t      g_cap  = 0;
-  uint8_t*    d_data = nullptr;  // batch: decoded TBs of the UEs without UCI
-  size_t      data_cap = 0;
+  DevBuf<float2>     d_grid;  // subframe grid (sync API)
+  DevBuf<float2>     d_ce;    // estimate grid uploaded from the host (sync API, channel->gpu absent)
+  DevBuf<float2>     d_sym;   // de-precoded symbols
+  DevBuf<int16_t>    d_q;     // LLRs
+  DevBuf<uint8_t>    d_c;     // unpacked scrambling sequence
+  DevBuf<PuschUe>    d_desc;
+  DevBuf<LlrItem>    d_llr;
+  DevBuf<ChestUlOut> d_out;   // per-UE outputs (sync API: one; batch: nof_ue)
+  DevBuf<float2>     d_bce;   // batch: per-UE estimate grids
+  DevBuf<int16_t>    d_g;     // batch: de-interleaved LLRs of the UEs without UCI
+  DevBuf<uint8_t>    d_data;  // batch: decoded TBs of the UEs without UCI
   uint32_t    last_nsym = 0, last_nllr = 0;  // the last host-sync decode's counts (srsran_pusch_gpu_last_soft)
-  uint8_t*    d_tx   = nullptr;  // transmit: descriptors and DMRS values of a batch
-  size_t      tx_cap = 0;
-  uint8_t*    d_txdata = nullptr;  // transmit (sync API): the payload
-  size_t      txdata_cap = 0;
+  DevBuf<uint8_t>    d_tx;      // transmit: descriptors and DMRS values of a batch
+  DevBuf<uint8_t>    d_txdata;  // transmit (sync API): the payload
 };
 
 uint32_t pusch_seed(uint16_t rnti, uint32_t nslot, uint32_t cell_id)  // sequences.c:119-122
@@ -340,7 +311,7 @@ hipStream_t chest_ul_stream(srsran_chest_ul_t* q) { return q && q->gpu ? ((Chest
 void*       chest_ul_scratch(srsran_chest_ul_t* q, size_t bytes)
 {
   ChestUlGpu* g = (ChestUlGpu*)q->gpu;
-  return grow((void**)&g->d_grid, &g->grid_cap, bytes) ? (void*)g->d_grid : nullptr;
+  return g->d_grid.reserve((bytes + sizeof(float2) - 1) / sizeof(float2)) ? (void*)g->d_grid.get() : nullptr;
 }
 void chest_ul_res_host_changed(srsran_chest_ul_res_t* res)
 {
@@ -455,9 +426,6 @@ void srsran_chest_ul_free(srsran_chest_ul_t* q)
       hipStreamSynchronize(g->stream);
       hipStreamDestroy(g->stream);
     }
-    hipFree(g->d_dmrs);
-    hipFree(g->d_grid);
-    hipFree(g->d_desc);
     delete g;
   }
   memset(q, 0, sizeof(*q));
@@ -477,9 +445,9 @@ int srsran_chest_ul_res_init(srsran_chest_ul_res_t* q, uint32_t max_prb)
   ChestUlResGpu* g = new ChestUlResGpu();
   g->nof_re        = q->nof_re;
   q->gpu           = g;
-  if (hipMalloc((void**)&g->d_ce, (size_t)std::max<uint32_t>(q->nof_re, 1) * sizeof(float2)) != hipSuccess ||
+  if (!g->d_ce.reserve(std::max<uint32_t>(q->nof_re, 1)) ||
       hipMemset(g->d_ce, 0, (size_t)std::max<uint32_t>(q->nof_re, 1) * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_out, sizeof(ChestUlOut)) != hipSuccess) {
+      !g->d_out.reserve(1)) {
     srsran_chest_ul_res_free(q);
     return SRSRAN_ERROR;
   }
@@ -506,12 +474,7 @@ void srsran_chest_ul_res_free(srsran_chest_ul_res_t* q)
     return;
   }
   free(q->ce);
-  ChestUlResGpu* g = (ChestUlResGpu*)q->gpu;
-  if (g) {
-    hipFree(g->d_ce);
-    hipFree(g->d_out);
-    delete g;
-  }
+  delete (ChestUlResGpu*)q->gpu;
   memset(q, 0, sizeof(*q));
 }
 
@@ -562,7 +525,7 @@ void srsran_chest_ul_pregen(srsran_chest_ul_t* q, srsran_refsignal_dmrs_pusch_cf
       }
     }
   }
-  if (!grow((void**)&g->d_dmrs, &g->dmrs_cap, h.size() * sizeof(float2)) ||
+  if (!g->d_dmrs.reserve(h.size()) ||
       hipMemcpy(g->d_dmrs, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
     fprintf(stderr, "[srsran_chest_ul] DMRS upload failed\n");
     return;
@@ -615,8 +578,8 @@ int srsran_chest_ul_estimate_pusch(srsran_chest_ul_t*     q,
       return SRSRAN_ERROR;
     }
   }
-  if (!grow((void**)&g->d_grid, &g->grid_cap, sf_re * sizeof(float2)) ||
-      !grow((void**)&g->d_desc, &g->desc_cap, sizeof(PuschUe))) {
+  if (!g->d_grid.reserve(sf_re) ||
+      !g->d_desc.reserve(1)) {
     return SRSRAN_ERROR;
   }
   u.grid = g->d_grid;
@@ -674,19 +637,6 @@ void srsran_pusch_free(srsran_pusch_t* q)
     if (st) {
       hipStreamSynchronize(st);
     }
-    hipFree(g->d_grid);
-    hipFree(g->d_ce);
-    hipFree(g->d_sym);
-    hipFree(g->d_q);
-    hipFree(g->d_c);
-    hipFree(g->d_desc);
-    hipFree(g->d_llr);
-    hipFree(g->d_out);
-    hipFree(g->d_bce);
-    hipFree(g->d_g);
-    hipFree(g->d_data);
-    hipFree(g->d_tx);
-    hipFree(g->d_txdata);
     delete g;
   }
   srsran_sch_free(&q->ul_sch);
@@ -753,11 +703,11 @@ int srsran_pusch_decode(srsran_pusch_t*        q,
   const uint32_t ncell = q->cell.nof_prb * SRSRAN_NRE, nsf = 2 * nsymb_slot(q->cell.cp);
   const size_t   sf_re = (size_t)ncell * nsf;
   const uint32_t nb    = cfg->grant.tb.nof_bits;
-  if (!grow((void**)&g->d_grid, &g->grid_cap, sf_re * sizeof(float2)) ||
-      !grow((void**)&g->d_sym, &g->sym_cap, (size_t)cfg->grant.nof_re * sizeof(float2)) ||
-      !grow((void**)&g->d_q, &g->q_cap, (size_t)nb * sizeof(int16_t)) ||
-      !grow((void**)&g->d_c, &g->c_cap, (size_t)nb) || !grow((void**)&g->d_desc, &g->desc_cap, sizeof(PuschUe)) ||
-      !grow((void**)&g->d_out, &g->out_cap, sizeof(ChestUlOut))) {
+  if (!g->d_grid.reserve(sf_re) ||
+      !g->d_sym.reserve((size_t)cfg->grant.nof_re) ||
+      !g->d_q.reserve((size_t)nb) ||
+      !g->d_c.reserve((size_t)nb) || !g->d_desc.reserve(1) ||
+      !g->d_out.reserve(1)) {
     return SRSRAN_ERROR;
   }
   // the estimate: the estimator's device copy when it is current, else the host's ce
@@ -766,7 +716,7 @@ int srsran_pusch_decode(srsran_pusch_t*        q,
   if (rg && rg->valid && rg->nof_re >= sf_re) {
     d_ce = rg->d_ce;
   } else {
-    if (!channel->ce || !grow((void**)&g->d_ce, &g->ce_cap, sf_re * sizeof(float2)) ||
+    if (!channel->ce || !g->d_ce.reserve(sf_re) ||
         hipMemcpyAsync(g->d_ce, channel->ce, sf_re * sizeof(float2), hipMemcpyHostToDevice, st) != hipSuccess) {
       return SRSRAN_ERROR;
     }
@@ -785,13 +735,13 @@ int srsran_pusch_decode(srsran_pusch_t*        q,
   u.dft_norm = 1.0f / sqrtf((float)M);
   LlrItem it{};
   memset(&it, 0, sizeof(it));
-  it.sym         = (const float*)g->d_sym;
+  it.sym         = (const float*)g->d_sym.get();
   it.llr         = g->d_q;
   it.n           = cfg->grant.nof_re;
   it.seed        = pusch_seed(cfg->rnti, 2 * (sf->tti % SRSRAN_NOF_SF_X_FRAME), q->cell.id);
   it.scramble    = 1;
   const bool uci = any_uci(cfg);
-  if (!grow((void**)&g->d_llr, &g->llr_cap, sizeof(LlrItem)) ||
+  if (!g->d_llr.reserve(1) ||
       hipMemcpyAsync(g->d_grid, sf_symbols, sf_re * sizeof(float2), hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemcpyAsync(g->d_desc, &u, sizeof(u), hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemcpyAsync(g->d_llr, &it, sizeof(it), hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -828,7 +778,7 @@ int srsran_pusch_gpu_last_soft(srsran_pusch_t* q, const cf_t** d_sym, uint32_t* 
   if (g->last_nsym == 0) {  // no host-sync decode yet, or a batch has reused the buffers since
     return SRSRAN_ERROR;
   }
-  *d_sym   = (const cf_t*)g->d_sym;
+  *d_sym   = (const cf_t*)g->d_sym.get();
   *nof_sym = g->last_nsym;
   *d_llr   = g->d_q;
   *nof_llr = g->last_nllr;
@@ -892,12 +842,12 @@ int srsran_pusch_gpu_decode_batch(srsran_pusch_t*              q,
     c_off[i] = c_tot;
     c_tot += any_uci(cfg) ? ((cfg->grant.tb.nof_bits + 15) & ~15u) : 0;
   }
-  if (!grow((void**)&g->d_desc, &g->desc_cap, nof_ue * sizeof(PuschUe)) ||
-      !grow((void**)&g->d_out, &g->out_cap, nof_ue * sizeof(ChestUlOut)) ||
-      !grow((void**)&g->d_bce, &g->bce_cap, ce_tot * sizeof(float2)) ||
-      !grow((void**)&g->d_sym, &g->sym_cap, sym_tot * sizeof(float2)) ||
-      !grow((void**)&g->d_q, &g->q_cap, q_tot * sizeof(int16_t)) || !grow((void**)&g->d_c, &g->c_cap, c_tot + 16) ||
-      !grow((void**)&g->d_llr, &g->llr_cap, nof_ue * sizeof(LlrItem))) {
+  if (!g->d_desc.reserve(nof_ue) ||
+      !g->d_out.reserve(nof_ue) ||
+      !g->d_bce.reserve(ce_tot) ||
+      !g->d_sym.reserve(sym_tot) ||
+      !g->d_q.reserve(q_tot) || !g->d_c.reserve(c_tot + 16) ||
+      !g->d_llr.reserve(nof_ue)) {
     return SRSRAN_ERROR;
   }
   std::vector<LlrItem> items(nof_ue);
@@ -960,7 +910,7 @@ int srsran_pusch_gpu_decode_batch(srsran_pusch_t*              q,
     g_tot += (cfg->grant.tb.nof_bits + 7) & ~7u;
     data_tot += cfg->grant.tb.tbs > 0 ? (((uint32_t)cfg->grant.tb.tbs / 8 + 64 + 15) & ~15u) : 0;
   }
-  if (!grow((void**)&g->d_g, &g->g_cap, g_tot * sizeof(int16_t)) || !grow((void**)&g->d_data, &g->data_cap, data_tot + 16)) {
+  if (!g->d_g.reserve(g_tot) || !g->d_data.reserve(data_tot + 16)) {
     return SRSRAN_ERROR;
   }
   std::vector<UlschBatchUe> ub(nof_ue);
@@ -1125,13 +1075,13 @@ int pusch_tx_run(srsran_pusch_t* owner, uint32_t n, const TxReq* r, std::vector<
   }
   desc.insert(desc.end(), extra.begin(), extra.end());
   const size_t o_dmrs = (desc.size() * sizeof(PuschTxUe) + 15) & ~(size_t)15;
-  if (!grow((void**)&g->d_tx, &g->tx_cap, o_dmrs + dmrs.size() * sizeof(cf_t))) {
+  if (!g->d_tx.reserve(o_dmrs + dmrs.size() * sizeof(cf_t))) {
     return SRSRAN_ERROR;
   }
   for (uint32_t i = 0; i < n; i++) {
     desc[i].dmrs = (const float2*)(g->d_tx + o_dmrs) + dmrs_off[i];
   }
-  *d_desc = (const PuschTxUe*)g->d_tx;
+  *d_desc = (const PuschTxUe*)g->d_tx.get();
   if (hipMemcpyAsync(g->d_tx, desc.data(), desc.size() * sizeof(PuschTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
       (!dmrs.empty() && hipMemcpyAsync(g->d_tx + o_dmrs, dmrs.data(), dmrs.size() * sizeof(cf_t), hipMemcpyHostToDevice,
                                        st) != hipSuccess) ||
@@ -1145,18 +1095,13 @@ int pusch_tx_run(srsran_pusch_t* owner, uint32_t n, const TxReq* r, std::vector<
 struct UeUlGpu {
   UlHopping hop;
   bool      hop_ok = false;
-  float2*   d_grid = nullptr;  // the grids of this object's entries of a batch
-  size_t    grid_cap = 0;
-  float2*   d_samp = nullptr;  // their samples before the normalisation
-  size_t    samp_cap = 0;
-  float2*   d_cfo = nullptr;   // srsran_vec_apply_cfo's phasors of cfo_freq (cfo_len samples)
-  size_t    cfo_cap = 0;
+  DevBuf<float2>  d_grid;  // the grids of this object's entries of a batch
+  DevBuf<float2>  d_samp;  // their samples before the normalisation
+  DevBuf<float2>  d_cfo;   // srsran_vec_apply_cfo's phasors of cfo_freq (cfo_len samples)
   float     cfo_freq = 0.0f;
   uint32_t  cfo_len = 0;
-  uint8_t*  d_io = nullptr;    // sync API: payload, then the output samples
-  size_t    io_cap = 0;
-  uint8_t*  d_ptx = nullptr;   // the PUCCH descriptors of a batch this object's scratch serves
-  size_t    ptx_cap = 0;
+  DevBuf<uint8_t> d_io;    // sync API: payload, then the output samples
+  DevBuf<uint8_t> d_ptx;   // the PUCCH descriptors of a batch this object's scratch serves
   // srsran_ue_ul_gpu_last
   const uint8_t* last_s = nullptr;
   const float2*  last_d = nullptr;
@@ -1244,8 +1189,8 @@ int srsran_pusch_encode(srsran_pusch_t*      q,
     fprintf(stderr, "[srsran_pusch] encoding from the soft buffer (data == NULL) is not provided\n");
     return SRSRAN_ERROR;
   }
-  if (sf_re == 0 || !grow((void**)&g->d_grid, &g->grid_cap, sf_re * sizeof(float2)) ||
-      !grow((void**)&g->d_txdata, &g->txdata_cap, (size_t)nbytes + 16) ||
+  if (sf_re == 0 || !g->d_grid.reserve(sf_re) ||
+      !g->d_txdata.reserve((size_t)nbytes + 16) ||
       hipMemcpyAsync(g->d_grid, sf_symbols, sf_re * sizeof(float2), hipMemcpyHostToDevice, st) != hipSuccess ||
       (nbytes && hipMemcpyAsync(g->d_txdata, data->ptr, nbytes, hipMemcpyHostToDevice, st) != hipSuccess)) {
     return SRSRAN_ERROR;
@@ -1327,11 +1272,6 @@ void srsran_ue_ul_free(srsran_ue_ul_t* q)
     if (st) {
       hipStreamSynchronize(st);
     }
-    hipFree(g->d_grid);
-    hipFree(g->d_samp);
-    hipFree(g->d_cfo);
-    hipFree(g->d_io);
-    hipFree(g->d_ptx);
     delete g;
   }
   srsran_ofdm_tx_free(&q->fft);
@@ -1512,8 +1452,8 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
     srsran_ue_ul_t* q = objs[o];
     UeUlGpu*        g = (UeUlGpu*)q->gpu;
     const size_t sf_re = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
-    if (!grow((void**)&g->d_grid, &g->grid_cap, count[o] * sf_re * sizeof(float2)) ||
-        !grow((void**)&g->d_samp, &g->samp_cap, (size_t)count[o] * q->fft.sf_sz * sizeof(float2))) {
+    if (!g->d_grid.reserve(count[o] * sf_re) ||
+        !g->d_samp.reserve((size_t)count[o] * q->fft.sf_sz)) {
       return SRSRAN_ERROR;
     }
   }
@@ -1581,15 +1521,15 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
   }
   if (!pdesc.empty()) {  // every PUCCH entry of every cell in one launch
     UeUlGpu* g0 = (UeUlGpu*)entries[0].q->gpu;
-    if (!grow((void**)&g0->d_ptx, &g0->ptx_cap, pdesc.size() * sizeof(PucchTxUe)) ||
+    if (!g0->d_ptx.reserve(pdesc.size() * sizeof(PucchTxUe)) ||
         hipMemcpyAsync(g0->d_ptx, pdesc.data(), pdesc.size() * sizeof(PucchTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
-        pucch_tx_launch((const PucchTxUe*)g0->d_ptx, (uint32_t)pdesc.size(), st) != hipSuccess) {
+        pucch_tx_launch((const PucchTxUe*)g0->d_ptx.get(), (uint32_t)pdesc.size(), st) != hipSuccess) {
       return SRSRAN_ERROR;
     }
   }
   for (size_t o = 0; o < objs.size(); o++) {
     UeUlGpu* g = (UeUlGpu*)objs[o]->gpu;
-    if (samples[o] && srsran_ofdm_tx_gpu(&objs[o]->fft, (const cf_t*)g->d_grid, (cf_t*)g->d_samp, 1, count[o], 1.0f, st) !=
+    if (samples[o] && srsran_ofdm_tx_gpu(&objs[o]->fft, (const cf_t*)g->d_grid.get(), (cf_t*)g->d_samp.get(), 1, count[o], 1.0f, st) !=
                           SRSRAN_SUCCESS) {
       return SRSRAN_ERROR;
     }
@@ -1613,7 +1553,7 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
       if (g->cfo_len != len || g->cfo_freq != f) {
         float c, s;
         cfo_phasor(f, &c, &s);
-        if (!grow((void**)&g->d_cfo, &g->cfo_cap, len * sizeof(float2)) ||
+        if (!g->d_cfo.reserve(len) ||
             cfo_table_launch(c, s, g->d_cfo, len, st) != hipSuccess) {
           return SRSRAN_ERROR;
         }
@@ -1690,10 +1630,10 @@ int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_
     if ((srsran_uci_cfg_total_ack(&pu) > 0 || pu.cqi.data_enable || pu.cqi.ri_len > 0 || data->uci.scheduling_request) &&
         cfg->cc_idx == 0) {  // PUCCH, over the PCell only (ue_ul.c:642-648): a batch of one
       hipStream_t st = sch_stream(&q->pusch.ul_sch);
-      if (!g->hop_ok || !q->out_buffer || !grow((void**)&g->d_io, &g->io_cap, sf_len * sizeof(cf_t))) {
+      if (!g->hop_ok || !q->out_buffer || !g->d_io.reserve(sf_len * sizeof(cf_t))) {
         return SRSRAN_ERROR;
       }
-      srsran_ue_ul_gpu_entry_t e   = {q, sf, cfg, &data->uci, nullptr, (cf_t*)g->d_io, nullptr};
+      srsran_ue_ul_gpu_entry_t e   = {q, sf, cfg, &data->uci, nullptr, (cf_t*)g->d_io.get(), nullptr};
       int                      ret = srsran_ue_ul_gpu_tx_batch(1, &e, st);
       if (ret == SRSRAN_SUCCESS &&
           hipMemcpyAsync(q->out_buffer, g->d_io, sf_len * sizeof(cf_t), hipMemcpyDeviceToHost, st) != hipSuccess) {
@@ -1723,7 +1663,7 @@ int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_
     fprintf(stderr, "[srsran_ue_ul] encoding from the soft buffer (data == NULL) is not provided\n");
     return SRSRAN_ERROR;
   }
-  if (!grow((void**)&g->d_io, &g->io_cap, o_out + sf_len * sizeof(cf_t)) ||
+  if (!g->d_io.reserve(o_out + sf_len * sizeof(cf_t)) ||
       (nbytes && hipMemcpyAsync(g->d_io, data->ptr, nbytes, hipMemcpyHostToDevice, st) != hipSuccess)) {
     return SRSRAN_ERROR;
   }

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/srsran_sch.h"
+#include "dev_buf.h"
 #include "devkey.h"
 #include "sch_kernel.h"
 #include "tdec_kernel.h"
@@ -151,9 +152,9 @@ bool inv_table(uint32_t cb_idx, uint32_t rv, bool tdec_layout, InvTable* out)
 
 // ---------------- soft buffer device arena ----------------
 struct SbGpu {
-  short*   d_buf   = nullptr;  // max_cb x stride int16
-  uint8_t* d_data  = nullptr;  // max_cb x data_stride bytes
-  uint8_t* d_flags = nullptr;  // [0, max_cb): cb_crc, [max_cb]: tb_crc
+  short*          d_buf = nullptr;  // max_cb x stride int16, from the arena (sb_arena_alloc / sb_arena_free)
+  DevBuf<uint8_t> d_data;           // max_cb x data_stride bytes
+  DevBuf<uint8_t> d_flags;          // [0, max_cb): cb_crc, [max_cb]: tb_crc
   uint32_t stride = 0, data_stride = 0;
   size_t   buf_bytes = 0;      // d_buf size (rounded as the arena hands it out)
   int      buf_dev   = -1;     // >= 0: d_buf lives in that device's soft-buffer arena
@@ -275,8 +276,7 @@ struct StageSlot {
   bool       used   = false;
   char*      h      = nullptr;  // pinned coherent host memory (stage_host_alloc)
   char*      hd     = nullptr;  // its device alias
-  char*      d      = nullptr;
-  size_t     cap    = 0;
+  DevBuf<char> d;               // same capacity
 };
 
 struct SchCtx {
@@ -287,38 +287,29 @@ struct SchCtx {
   uint32_t    ring_next = 0;
   srsran_amd::StageFence    fence;  // the copy kernel's "slot read" words (stage_copy.h)
   srsran_amd::StreamHandoff ho;     // stream of the previous batch (device-side reuse of slots and scratch)
-  uint8_t*    d_cbout = nullptr;
-  uint8_t*    d_noi = nullptr;
-  uint8_t*    d_crc_ok = nullptr;
-  size_t      slot_cap = 0;
+  DevBuf<uint8_t> d_cbout;   // SCH_SLOT_BYTES a slot
+  DevBuf<uint8_t> d_noi;     // a byte a slot
+  DevBuf<uint8_t> d_crc_ok;  // a byte a slot; the three grow together
   // synchronous decode scratch
-  int16_t*    d_e = nullptr;
-  size_t      e_cap = 0;
-  uint8_t*    d_data = nullptr;
-  int32_t*    d_res = nullptr;
-  float*      d_avg = nullptr;
-  uint8_t*    h_io = nullptr;  // pinned: flags in/out, result, avg
-  uint8_t*    d_zero = nullptr;  // a cleared cb_crc flag for new transmissions
+  DevBuf<int16_t> d_e;       // int8 values with llr_is_8bit
+  DevBuf<uint8_t> d_data;
+  DevBuf<int32_t> d_res;
+  DevBuf<float>   d_avg;
+  PinBuf<uint8_t> h_io;      // flags in/out, result, avg
+  DevBuf<uint8_t> d_zero;    // a cleared cb_crc flag for new transmissions
   bool        used = false;
-  int16_t*    d_ul = nullptr;    // srsran_ulsch_decode: q then g bits
-  size_t      ul_cap = 0;
-  UlDeint*    d_uldesc = nullptr;  // srsran_ulsch_gpu_decode_batch descriptors (device)
-  UlDeint*    h_uldesc = nullptr;  // their pinned staging
+  DevBuf<int16_t> d_ul;      // srsran_ulsch_decode: q then g bits
+  DevBuf<UlDeint> d_uldesc;  // srsran_ulsch_gpu_decode_batch descriptors (device)
+  PinBuf<UlDeint> h_uldesc;  // their pinned staging, grown with d_uldesc
   hipEvent_t  uldesc_used = nullptr;  // recorded after the de-interleaver launch that reads them
   bool        uldesc_live = false;
-  size_t      uldesc_cap = 0;
-  uint8_t*    d_uci = nullptr;     // srsran_ulsch_decode with UCI: descriptors, results, sequence
-  size_t      uci_cap = 0;
-  uint8_t*    d_ubs = nullptr;     // the batched UL-SCH receive: descriptors and results (device)
-  size_t      dubs_cap = 0;
-  uint8_t*    h_ubs = nullptr;     // its pinned staging
-  size_t      hubs_cap = 0;
-  uint8_t*    d_enc = nullptr;     // DL-SCH encode: descriptors, TB CRCs, unpacked e bits, staging
-  size_t      enc_cap = 0;
-  uint8_t*    d_ultx = nullptr;    // UL-SCH transmit: descriptors, UCI bit lists, e / g / q bits, symbols
-  size_t      ultx_cap = 0;
-  short*      d_wide = nullptr;    // llr_is_8bit, K <= 800: the widened soft buffers the 16-bit decoders read
-  size_t      wide_cap = 0;        // rows of kWideStride
+  DevBuf<uint8_t> d_uci;     // srsran_ulsch_decode with UCI: descriptors, results, sequence
+  DevBuf<uint8_t> d_ubs;     // the batched UL-SCH receive: descriptors and results (device)
+  PinBuf<uint8_t> h_ubs;     // its pinned staging
+  DevBuf<uint8_t> d_enc;     // DL-SCH encode: descriptors, TB CRCs, unpacked e bits, staging
+  DevBuf<uint8_t> d_ultx;    // UL-SCH transmit: descriptors, UCI bit lists, e / g / q bits, symbols
+  DevBuf<short>   d_wide;    // llr_is_8bit, K <= 800: the widened soft buffers the 16-bit decoders read
+  size_t      wide_cap = 0;  // rows of kWideStride in d_wide
 };
 
 constexpr uint32_t kWideStride = 4096;  // int16 values a widened row (>= 3 (800 + 32) + 12 and the decoders' reads)
@@ -348,21 +339,6 @@ void drain_batches(SchCtx* x)
   } else {
     srsran_amd::handoff_drain(x->ho);
   }
-}
-
-bool grow_dev(void** p, size_t* cap, size_t need)
-{
-  if (*cap >= need) {
-    return true;
-  }
-  hipFree(*p);
-  *p = nullptr;
-  if (hipMalloc(p, need) != hipSuccess) {
-    *cap = 0;
-    return false;
-  }
-  *cap = need;
-  return true;
 }
 
 struct Plan {
@@ -476,11 +452,9 @@ int enqueue_batch(srsran_sch_t* q, uint32_t ntb, const srsran_dlsch_gpu_tb_t* tb
     }
     if (wide.size() > x->wide_cap) {
       drain_batches(x);
-      hipFree(x->d_wide);
-      x->d_wide         = nullptr;
       const size_t rows = std::max(wide.size() * 2, (size_t)16);
-      if (hipMalloc((void**)&x->d_wide, rows * kWideStride * sizeof(short)) != hipSuccess) {
-        x->wide_cap = 0;
+      x->wide_cap       = 0;
+      if (!x->d_wide.reserve(rows * kWideStride)) {
         return SRSRAN_ERROR;
       }
       x->wide_cap = rows;
@@ -570,10 +544,10 @@ int enqueue_batch(srsran_sch_t* q, uint32_t ntb, const srsran_dlsch_gpu_tb_t* tb
   }
   wait.stop();
   srsran_amd::HostScope launch(srsran_amd::HP_SCH_LAUNCH);
-  if (bytes > st.cap) {  // every slot of the ring grows now: no allocation when the others come round
+  if (bytes > st.d.cap()) {  // every slot of the ring grows now: no allocation when the others come round
     const size_t cap = std::max(bytes * 2, (size_t)4096);
     for (StageSlot& r : x->ring) {
-      if (r.cap >= cap) {
+      if (r.d.cap() >= cap) {
         continue;
       }
       if (r.used) {
@@ -583,32 +557,20 @@ int enqueue_batch(srsran_sch_t* q, uint32_t ntb, const srsran_dlsch_gpu_tb_t* tb
           srsran_amd::handoff_drain(x->ho);
         }
       }
-      hipHostFree(r.h);
-      hipFree(r.d);
-      r.h = nullptr;
-      r.d = nullptr;
+      hipHostFree(r.h);  // stage_host_alloc's memory (stage_copy.h)
+      r.d.reset();
       r.h = (char*)srsran_amd::stage_host_alloc(cap, (void**)&r.hd);
-      if (!r.h || hipMalloc((void**)&r.d, cap) != hipSuccess) {
-        r.cap = 0;
+      if (!r.h || !r.d.reserve(cap)) {
         return SRSRAN_ERROR;
       }
-      r.cap = cap;
     }
   }
-  if (nslots > x->slot_cap) {
+  if (nslots * (size_t)SCH_SLOT_BYTES > x->d_cbout.cap() || nslots > x->d_noi.cap() ||
+      nslots > x->d_crc_ok.cap()) {
     drain_batches(x);
-    {
-      const size_t cap = std::max((size_t)nslots * 2, (size_t)64);
-      hipFree(x->d_cbout);
-      hipFree(x->d_noi);
-      hipFree(x->d_crc_ok);
-      x->d_cbout = x->d_noi = x->d_crc_ok = nullptr;
-      if (hipMalloc((void**)&x->d_cbout, cap * SCH_SLOT_BYTES) != hipSuccess ||
-          hipMalloc((void**)&x->d_noi, cap) != hipSuccess || hipMalloc((void**)&x->d_crc_ok, cap) != hipSuccess) {
-        x->slot_cap = 0;
-        return SRSRAN_ERROR;
-      }
-      x->slot_cap = cap;
+    const size_t cap = std::max((size_t)nslots * 2, (size_t)64);
+    if (!x->d_cbout.reserve(cap * SCH_SLOT_BYTES) || !x->d_noi.reserve(cap) || !x->d_crc_ok.reserve(cap)) {
+      return SRSRAN_ERROR;
     }
   }
   uint32_t max_tbs = 0;
@@ -863,13 +825,27 @@ namespace {
 std::mutex g_rm_mu;
 struct RmCtx {  // one per device: the host-synchronous srsran_rm_turbo_rx_lut_ scratch
   hipStream_t stream = nullptr;
-  int16_t*    d_in   = nullptr;
-  size_t      in_cap = 0;
-  int16_t*    d_out  = nullptr;
-  RmSlot*     d_slot = nullptr;
-  uint8_t*    d_zero = nullptr;
+  DevBuf<int16_t> d_in;  // int8 values in srsran_rm_turbo_rx_lut_8bit
+  DevBuf<int16_t> d_out;
+  DevBuf<RmSlot>  d_slot;
+  DevBuf<uint8_t> d_zero;
 };
-std::map<int, RmCtx> g_rm;
+
+// the current device's context with `in_bytes` of input scratch, or nullptr.  The contexts live for the process:
+// the map is never destroyed, so no hipFree runs after the runtime is gone.
+RmCtx* rm_ctx(size_t in_bytes)
+{
+  static auto& ctxs = *new std::map<int, RmCtx>;
+  RmCtx&       c    = ctxs[cur_dev()];
+  if (!c.stream) {
+    if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess ||
+        !c.d_out.reserve(SOFTBUFFER_SIZE) || !c.d_slot.reserve(1) || !c.d_zero.reserve(8) ||
+        hipMemset(c.d_zero, 0, 8) != hipSuccess) {
+      return nullptr;
+    }
+  }
+  return c.d_in.reserve((std::max<size_t>(in_bytes, 1) + 1) / 2) ? &c : nullptr;
+}
 }  // namespace
 
 int srsran_rm_turbo_rx_lut_(int16_t* input,
@@ -891,18 +867,11 @@ int srsran_rm_turbo_rx_lut_(int16_t* input,
     return SRSRAN_ERROR;
   }
   std::lock_guard<std::mutex> lk(g_rm_mu);
-  RmCtx&                      c = g_rm[cur_dev()];
-  if (!c.stream) {
-    if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void**)&c.d_out, (size_t)SOFTBUFFER_SIZE * sizeof(int16_t)) != hipSuccess ||
-        hipMalloc((void**)&c.d_slot, sizeof(RmSlot)) != hipSuccess || hipMalloc((void**)&c.d_zero, 8) != hipSuccess ||
-        hipMemset(c.d_zero, 0, 8) != hipSuccess) {
-      return SRSRAN_ERROR;
-    }
-  }
-  if (!grow_dev((void**)&c.d_in, &c.in_cap, std::max<size_t>(in_len, 1) * sizeof(int16_t))) {
+  RmCtx*                      cp = rm_ctx((size_t)in_len * sizeof(int16_t));
+  if (!cp) {
     return SRSRAN_ERROR;
   }
+  RmCtx& c = *cp;
   RmSlot s;
   s.e    = c.d_in;
   s.sb   = c.d_out;
@@ -942,20 +911,13 @@ int srsran_rm_turbo_rx_lut_8bit(int8_t* input, int8_t* output, uint32_t in_len, 
     return SRSRAN_ERROR;
   }
   std::lock_guard<std::mutex> lk(g_rm_mu);
-  RmCtx&                      c = g_rm[cur_dev()];
-  if (!c.stream) {
-    if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void**)&c.d_out, (size_t)SOFTBUFFER_SIZE * sizeof(int16_t)) != hipSuccess ||
-        hipMalloc((void**)&c.d_slot, sizeof(RmSlot)) != hipSuccess || hipMalloc((void**)&c.d_zero, 8) != hipSuccess ||
-        hipMemset(c.d_zero, 0, 8) != hipSuccess) {
-      return SRSRAN_ERROR;
-    }
-  }
-  if (!grow_dev((void**)&c.d_in, &c.in_cap, std::max<size_t>(in_len, 1))) {
+  RmCtx*                      cp = rm_ctx(in_len);
+  if (!cp) {
     return SRSRAN_ERROR;
   }
-  int8_t* d_in  = (int8_t*)c.d_in;
-  int8_t* d_out = (int8_t*)c.d_out;
+  RmCtx&  c     = *cp;
+  int8_t* d_in  = (int8_t*)c.d_in.get();
+  int8_t* d_out = (int8_t*)c.d_out.get();
   hipMemcpyAsync(d_in, input, in_len, hipMemcpyHostToDevice, c.stream);
   hipMemcpyAsync(d_out, output, t.len, hipMemcpyHostToDevice, c.stream);
   if (srsran_amd::rm8_rx_launch(d_in, d_out, t.d, in_len, t.len, t.N, c.stream) != hipSuccess) {
@@ -998,8 +960,7 @@ int srsran_softbuffer_rx_init_guru(srsran_softbuffer_rx_t* q, uint32_t max_cb, u
   if (!q->buffer_f || !q->data || !q->cb_crc ||
       !(g->buf_bytes = std::max<size_t>((size_t)max_cb * g->stride * sizeof(int16_t), 8),
         g->d_buf     = (short*)sb_arena_alloc(g->buf_bytes, &g->buf_dev)) ||
-      hipMalloc((void**)&g->d_data, std::max<size_t>((size_t)max_cb * g->data_stride, 8)) != hipSuccess ||
-      hipMalloc((void**)&g->d_flags, max_cb + 1) != hipSuccess) {
+      !g->d_data.reserve(std::max<size_t>((size_t)max_cb * g->data_stride, 8)) || !g->d_flags.reserve(max_cb + 1)) {
     srsran_softbuffer_rx_free(q);
     return SRSRAN_ERROR;
   }
@@ -1087,9 +1048,7 @@ void srsran_softbuffer_rx_free(srsran_softbuffer_rx_t* q)
     DevScope ds(g->dev);
     hipDeviceSynchronize();
     sb_arena_free(g->d_buf, g->buf_bytes, g->buf_dev);
-    hipFree(g->d_data);
-    hipFree(g->d_flags);
-    delete g;
+    delete g;  // d_data, d_flags: released with their own device current
   }
   free(q->buffer_f);
   free(q->data);
@@ -1128,10 +1087,8 @@ int srsran_sch_init(srsran_sch_t* q)
   if (hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&x->copy, hipStreamNonBlocking) != hipSuccess ||
       srsran_amd::ring_event_create(&x->done) != hipSuccess || !init_ring(x) ||
-      hipMalloc((void**)&x->d_data, kDataCap) != hipSuccess || hipMalloc((void**)&x->d_res, 16) != hipSuccess ||
-      hipMalloc((void**)&x->d_avg, 16) != hipSuccess ||
-      hipHostMalloc((void**)&x->h_io, 256, hipHostMallocDefault) != hipSuccess ||
-      hipMalloc((void**)&x->d_zero, 8) != hipSuccess || hipMemset(x->d_zero, 0, 8) != hipSuccess) {
+      !x->d_data.reserve(kDataCap) || !x->d_res.reserve(4) || !x->d_avg.reserve(4) || !x->h_io.reserve(256) ||
+      !x->d_zero.reserve(8) || hipMemset(x->d_zero, 0, 8) != hipSuccess) {
     srsran_sch_free(q);
     return SRSRAN_ERROR;
   }
@@ -1164,32 +1121,13 @@ void srsran_sch_free(srsran_sch_t* q)
       if (st.done) {
         hipEventDestroy(st.done);
       }
-      hipHostFree(st.h);
-      hipFree(st.d);
+      hipHostFree(st.h);  // stage_host_alloc's memory (stage_copy.h)
     }
     srsran_amd::stage_fence_free(x->fence);
     srsran_amd::handoff_free(x->ho);
-    hipFree(x->d_cbout);
-    hipFree(x->d_noi);
-    hipFree(x->d_crc_ok);
-    hipFree(x->d_e);
-    hipFree(x->d_data);
-    hipFree(x->d_res);
-    hipFree(x->d_avg);
-    hipHostFree(x->h_io);
-    hipFree(x->d_zero);
-    hipFree(x->d_ul);
-    hipFree(x->d_uldesc);
-    hipHostFree(x->h_uldesc);
     if (x->uldesc_used) {
       hipEventDestroy(x->uldesc_used);
     }
-    hipFree(x->d_uci);
-    hipFree(x->d_ubs);
-    hipHostFree(x->h_ubs);
-    hipFree(x->d_enc);
-    hipFree(x->d_ultx);
-    hipFree(x->d_wide);
     delete x;
   }
   srsran_tdec_free(&q->decoder);
@@ -1243,7 +1181,7 @@ static int dlsch_decode_sync(srsran_sch_t*       q,
   const uint32_t nbe = cfg->grant.tb[tb_idx].nof_bits;
   const size_t   esz = q->llr_is_8bit ? sizeof(int8_t) : sizeof(int16_t);  // e_bits are int8 with llr_is_8bit
   hipStreamSynchronize(x->stream);
-  if (!d_e_bits && !grow_dev((void**)&x->d_e, &x->e_cap, std::max<size_t>(nbe, 1) * esz)) {
+  if (!d_e_bits && !x->d_e.reserve((std::max<size_t>(nbe, 1) * esz + 1) / 2)) {
     return SRSRAN_ERROR;
   }
   // the host cb_crc mirror is authoritative for the synchronous API
@@ -1842,14 +1780,8 @@ static int ulsch_decode_impl(srsran_sch_t*       q,
   }
 
   SchCtx* x = (SchCtx*)q->gpu;
-  if (2 * (size_t)nb > x->ul_cap) {
-    hipFree(x->d_ul);
-    x->d_ul   = nullptr;
-    x->ul_cap = 0;
-    if (hipMalloc((void**)&x->d_ul, 2 * (size_t)nb * sizeof(int16_t)) != hipSuccess) {
-      return SRSRAN_ERROR;
-    }
-    x->ul_cap = 2 * (size_t)nb;
+  if (!x->d_ul.reserve(2 * (size_t)nb)) {
+    return SRSRAN_ERROR;
   }
   int16_t* d_q = d_q_ext ? d_q_ext : x->d_ul;
   int16_t* d_g = x->d_ul + nb;
@@ -1880,10 +1812,10 @@ static int ulsch_decode_impl(srsran_sch_t*       q,
   // ---- device scratch: descriptors, results, sequence ----
   const bool   up_c = p.need_c && !d_c_ext;
   const size_t scr  = align16(sizeof(UlsUciScratch)) + (up_c ? (size_t)nb : 0);
-  if (!grow_dev((void**)&x->d_uci, &x->uci_cap, scr)) {
+  if (!x->d_uci.reserve(scr)) {
     return SRSRAN_ERROR;
   }
-  UlsUciScratch* d_s = (UlsUciScratch*)x->d_uci;
+  UlsUciScratch* d_s = (UlsUciScratch*)x->d_uci.get();
   const uint8_t* d_c = up_c ? x->d_uci + align16(sizeof(UlsUciScratch)) : d_c_ext;
   srsran_cqi_cfg_t& cq = cfg->uci_cfg.cqi;
   UlsUciScratch  h;
@@ -2075,17 +2007,8 @@ int ulsch_decode_batch_dev(srsran_sch_t* q, uint32_t n, UlschBatchUe* ues, const
   const size_t dev_need = o_avg + align16(nl * sizeof(float));
   const size_t h_cqi = dev_need, h_back = h_cqi + align16(m * sizeof(UciDesc));
   const size_t back_len = dev_need - o_out, h_need = h_back + back_len + data_bytes;
-  if (!grow_dev((void**)&x->d_ubs, &x->dubs_cap, dev_need)) {
+  if (!x->d_ubs.reserve(dev_need) || !x->h_ubs.reserve(h_need)) {
     return SRSRAN_ERROR;
-  }
-  if (h_need > x->hubs_cap) {
-    hipHostFree(x->h_ubs);
-    x->h_ubs    = nullptr;
-    x->hubs_cap = 0;
-    if (hipHostMalloc((void**)&x->h_ubs, h_need, hipHostMallocDefault) != hipSuccess) {
-      return SRSRAN_ERROR;
-    }
-    x->hubs_cap = h_need;
   }
   uint8_t* d = x->d_ubs;
   uint8_t* h = x->h_ubs;
@@ -2234,18 +2157,11 @@ int srsran_ulsch_gpu_decode_batch(srsran_sch_t*                q,
   if (!x->uldesc_used && hipEventCreateWithFlags(&x->uldesc_used, hipEventDisableTiming) != hipSuccess) {
     return SRSRAN_ERROR;
   }
-  if (nof_tb > x->uldesc_cap) {
-    hipFree(x->d_uldesc);
-    hipHostFree(x->h_uldesc);
-    x->d_uldesc   = nullptr;
-    x->h_uldesc   = nullptr;
-    x->uldesc_cap = 0;
+  if (nof_tb > x->d_uldesc.cap() || nof_tb > x->h_uldesc.cap()) {
     const size_t cap = std::max<size_t>(2 * nof_tb, 64);
-    if (hipMalloc((void**)&x->d_uldesc, cap * sizeof(UlDeint)) != hipSuccess ||
-        hipHostMalloc((void**)&x->h_uldesc, cap * sizeof(UlDeint), hipHostMallocDefault) != hipSuccess) {
+    if (!x->d_uldesc.reserve(cap) || !x->h_uldesc.reserve(cap)) {
       return SRSRAN_ERROR;
     }
-    x->uldesc_cap = cap;
   }
   if (nof_tb) {
     memcpy(x->h_uldesc, desc.data(), nof_tb * sizeof(UlDeint));
@@ -2353,7 +2269,7 @@ int srsran_dlsch_gpu_encode_batch(srsran_sch_t* q, uint32_t nof_tb, const srsran
   // device scratch: [EncTb x ntb][EncCb x ncb][crc x ntb][unpacked e bits]
   const size_t o_cb = align16(nof_tb * sizeof(EncTb)), o_crc = o_cb + align16(cb.size() * sizeof(EncCb));
   const size_t o_e = o_crc + align16(nof_tb * sizeof(uint32_t)), need = o_e + e_tot;
-  if (!grow_dev((void**)&x->d_enc, &x->enc_cap, need)) {
+  if (!x->d_enc.reserve(need)) {
     return SRSRAN_ERROR;
   }
   uint32_t* d_crc = (uint32_t*)(x->d_enc + o_crc);
@@ -2366,7 +2282,7 @@ int srsran_dlsch_gpu_encode_batch(srsran_sch_t* q, uint32_t nof_tb, const srsran
     c.e      = d_e + (size_t)(uintptr_t)c.e;
     c.tb_crc = d_crc + (size_t)(uintptr_t)c.tb_crc;
   }
-  const EncTb* d_tb = (const EncTb*)x->d_enc;
+  const EncTb* d_tb = (const EncTb*)x->d_enc.get();
   const EncCb* d_cb = (const EncCb*)(x->d_enc + o_cb);
   if (hipMemcpyAsync(x->d_enc, tb.data(), nof_tb * sizeof(EncTb), hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemcpyAsync(x->d_enc + o_cb, cb.data(), cb.size() * sizeof(EncCb), hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -2720,7 +2636,7 @@ int ulsch_tx_prepare(srsran_sch_t* q, uint32_t n, UlschTxJob* jobs, PuschTxUe* d
   const size_t o_cb = align16(tb.size() * sizeof(EncTb)), o_lists = o_cb + align16(cb.size() * sizeof(EncCb));
   const size_t o_crc = o_lists + align16(lists.size()), o_e = o_crc + align16(tb.size() * sizeof(uint32_t));
   const size_t o_bits = o_e + e_tot, o_sym = o_bits + bits_tot, need = o_sym + sym_tot * sizeof(float2);
-  if (!grow_dev((void**)&x->d_ultx, &x->ultx_cap, need)) {
+  if (!x->d_ultx.reserve(need)) {
     return SRSRAN_ERROR;
   }
   uint8_t*  base  = x->d_ultx;

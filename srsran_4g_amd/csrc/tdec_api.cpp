@@ -22,6 +22,7 @@
 
 #include "../../include/srsran_tdec.h"
 #include "stage_copy.h"
+#include "dev_buf.h"
 #include "devkey.h"
 #include "tdec_kernel.h"
 #include "tdec8bit_kernel.h"
@@ -193,14 +194,12 @@ int nsb_for(const srsran_tdec_t* h, uint32_t K)
 // Per-object device context (the reference's app/ext/syst/parity buffers).
 struct Ctx {
   hipStream_t stream = nullptr;
-  short*      d_in   = nullptr;  // one code block input (max SB layout)
-  uint8_t*    d_out  = nullptr;
-  short*      d_state = nullptr; // saved LDS state between srsran_tdec_iteration calls
-  size_t      state_elems = 0;
+  DevBuf<short>   d_in;     // one code block input (max SB layout)
+  DevBuf<uint8_t> d_out;
+  DevBuf<short>   d_state;  // saved LDS state between srsran_tdec_iteration calls
   // batch scratch
-  short*      d_bin  = nullptr;
-  uint8_t*    d_bout = nullptr;
-  size_t      bin_elems = 0, bout_bytes = 0;
+  DevBuf<short>   d_bin;
+  DevBuf<uint8_t> d_bout;
 };
 
 const size_t kMaxIn = 3 * (SRSRAN_TCOD_MAX_LEN_CB + 32) + SRSRAN_TCOD_TOTALTAIL;
@@ -227,23 +226,6 @@ int enqueue(const Config* c, const short* d_in, uint32_t in_stride, int layout_s
     return SRSRAN_ERROR;
   }
   return SRSRAN_SUCCESS;
-}
-
-bool grow(void** p, size_t* have, size_t need)
-{
-  if (*have >= need) {
-    return true;
-  }
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (hipMalloc(p, need) != hipSuccess) {
-    *have = 0;
-    return false;
-  }
-  *have = need;
-  return true;
 }
 
 // x^(8m) mod CRC24A / CRC24B, m = 0..768, for the in-kernel CB CRC (device, built once)
@@ -585,8 +567,7 @@ int srsran_tdec_init_manual(srsran_tdec_t* h, uint32_t max_long_cb, srsran_tdec_
   }
   Ctx* c = new Ctx();
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&c->d_in, kMaxIn * sizeof(short)) != hipSuccess ||
-      hipMalloc(&c->d_out, SRSRAN_TCOD_MAX_LEN_CB / 8) != hipSuccess) {
+      !c->d_in.reserve(kMaxIn) || !c->d_out.reserve(SRSRAN_TCOD_MAX_LEN_CB / 8)) {
     delete c;
     return SRSRAN_ERROR;
   }
@@ -609,11 +590,6 @@ void srsran_tdec_free(srsran_tdec_t* h)
       hipStreamSynchronize(c->stream);
       hipStreamDestroy(c->stream);
     }
-    hipFree(c->d_in);
-    hipFree(c->d_out);
-    hipFree(c->d_state);
-    hipFree(c->d_bin);
-    hipFree(c->d_bout);
     delete c;
   }
   memset(h, 0, sizeof(*h));
@@ -664,7 +640,7 @@ void srsran_tdec_iteration(srsran_tdec_t* h, int16_t* input, uint8_t* output)
     return;
   }
   const size_t st = 2 * (size_t)c->proto.xyw;
-  if (!grow((void**)&ctx->d_state, &ctx->state_elems, st * sizeof(short))) {
+  if (!ctx->d_state.reserve(st)) {
     return;
   }
   if (h->n_iter == 0) {
@@ -722,8 +698,7 @@ int srsran_tdec_run_all_batch(srsran_tdec_t* h,
   }
   const size_t in_elems  = (size_t)in_stride * (nof_cb - 1) + len;
   const size_t out_bytes = (size_t)nof_cb * (long_cb / 8);
-  if (!grow((void**)&ctx->d_bin, &ctx->bin_elems, in_elems * sizeof(short)) ||
-      !grow((void**)&ctx->d_bout, &ctx->bout_bytes, out_bytes)) {
+  if (!ctx->d_bin.reserve(in_elems) || !ctx->d_bout.reserve(out_bytes)) {
     return SRSRAN_ERROR;
   }
   hipMemcpyAsync(ctx->d_bin, input, in_elems * sizeof(short), hipMemcpyHostToDevice, ctx->stream);
@@ -768,9 +743,8 @@ namespace {
 constexpr int kPoolStreams = 4;
 // Device descriptors of one fused multi-size launch (per decoder class).
 struct MultiDesc {
-  char*      h_stage = nullptr;  // pinned: TdecArgs[n] | first[n]
-  char*      d_stage = nullptr;
-  size_t     cap     = 0;
+  PinBuf<char> h_stage;          // pinned: TdecArgs[n] | first[n]
+  DevBuf<char> d_stage;          // same capacity
   hipEvent_t copied  = nullptr;  // the last upload from h_stage finished
   bool       used    = false;
 };
@@ -1009,18 +983,13 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
     if (m.used) {
       hipEventSynchronize(m.copied);
     }
-    if (need > m.cap) {
+    if (need > m.h_stage.cap() || need > m.d_stage.cap()) {
       hipStreamSynchronize(st);
-      hipHostFree(m.h_stage);
-      hipFree(m.d_stage);
-      m.h_stage = m.d_stage = nullptr;
-      m.cap                 = 0;
-      if (hipHostMalloc((void**)&m.h_stage, 2 * need) != hipSuccess || hipMalloc((void**)&m.d_stage, 2 * need) != hipSuccess) {
+      if (!m.h_stage.reserve(2 * need) || !m.d_stage.reserve(2 * need)) {
         return SRSRAN_ERROR;
       }
-      m.cap = 2 * need;
     }
-    TdecArgs* ha    = reinterpret_cast<TdecArgs*>(m.h_stage);
+    TdecArgs* ha    = reinterpret_cast<TdecArgs*>(m.h_stage.get());
     uint32_t* hf    = reinterpret_cast<uint32_t*>(m.h_stage + abyte);
     uint32_t  nblk  = 0;
     size_t    lds   = 0;
@@ -1054,7 +1023,7 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
     }
     hipEventRecord(m.copied, st);
     m.used = true;
-    const TdecArgs* dg = reinterpret_cast<const TdecArgs*>(m.d_stage);
+    const TdecArgs* dg = reinterpret_cast<const TdecArgs*>(m.d_stage.get());
     const uint32_t* df = reinterpret_cast<const uint32_t*>(m.d_stage + abyte);
     if ((kind == 2   ? (nsbc == 16  ? (w8 ? tdecs16w8::multi_launch(dg, df, (int)n, nblk, lds, st)
                                           : tdecs16::multi_launch(dg, df, (int)n, nblk, lds, st))
@@ -1175,11 +1144,11 @@ int srsran_tdec_run_all_8bit(srsran_tdec_t* h, int8_t* input, uint8_t* output, u
   Ctx*           ctx = (Ctx*)h->gpu;
   const bool     sb  = !h->force_not_sb;
   const uint32_t len = sb ? 3 * (long_cb + 32) + 12 : 3 * long_cb + 12;
-  if (!grow((void**)&ctx->d_bin, &ctx->bin_elems, len) || !grow((void**)&ctx->d_bout, &ctx->bout_bytes, long_cb / 8)) {
+  if (!ctx->d_bin.reserve((len + 1) / 2) || !ctx->d_bout.reserve(long_cb / 8)) {  // len int8 in the short buffer
     return SRSRAN_ERROR;
   }
   hipMemcpyAsync(ctx->d_bin, input, len, hipMemcpyHostToDevice, ctx->stream);
-  int ret = srsran_tdec_gpu_run_batch_8bit(long_cb, (const int8_t*)ctx->d_bin, len, sb ? 1 : 0, ctx->d_bout, 1,
+  int ret = srsran_tdec_gpu_run_batch_8bit(long_cb, (const int8_t*)ctx->d_bin.get(), len, sb ? 1 : 0, ctx->d_bout, 1,
                                            nof_iterations, ctx->stream);
   if (ret != SRSRAN_SUCCESS) {
     return ret;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/srsran_sch.h"
+#include "dev_buf.h"
 #include "devkey.h"
 #include "enc_kernel.h"
 
@@ -23,8 +24,7 @@ namespace {
 using srsran_amd::RmTxLut;
 
 struct TcodGpu {
-  uint8_t* d_in  = nullptr;
-  uint8_t* d_out = nullptr;
+  srsran_amd::DevBuf<uint8_t> d_in, d_out;
 };
 
 // rm_turbo.c:72-73 (36.212 Table 5.1.4-1): the inter-column permutation of the sub-block interleaver
@@ -158,8 +158,7 @@ int srsran_tcod_init(srsran_tcod_t* h, uint32_t max_long_cb)
   }
   TcodGpu* g = new TcodGpu();
   h->gpu     = g;
-  if (hipMalloc((void**)&g->d_in, max_long_cb) != hipSuccess ||
-      hipMalloc((void**)&g->d_out, 3 * (size_t)max_long_cb + 12) != hipSuccess) {
+  if (!g->d_in.reserve(max_long_cb) || !g->d_out.reserve(3 * (size_t)max_long_cb + 12)) {
     srsran_tcod_free(h);
     return SRSRAN_ERROR;
   }
@@ -173,10 +172,7 @@ void srsran_tcod_free(srsran_tcod_t* h)
     return;
   }
   if (h->gpu) {
-    TcodGpu* g = (TcodGpu*)h->gpu;
-    hipFree(g->d_in);
-    hipFree(g->d_out);
-    delete g;
+    delete (TcodGpu*)h->gpu;
   }
   memset(h, 0, sizeof(*h));
 }

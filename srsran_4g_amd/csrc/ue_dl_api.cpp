@@ -20,6 +20,7 @@
 #include "../../include/srsran_phich.h"
 #include "chest_kernel.h"
 #include "csi_kernel.h"
+#include "dev_buf.h"
 #include "pdsch_internal.h"
 #include "stage_copy.h"
 #include "stage_timing.h"
@@ -36,12 +37,11 @@ struct UeDlGpu {
   // subframe indices, kStageRing slots of cap entries, in pinned coherent host memory that the estimator
   // reads in place (d_sf: its device alias) -- no upload, which in the stream cost a copy launch and ~20 us
   // of GPU idle per batch (gpurun_out r04j rocprof trace)
-  uint32_t*  h_sf   = nullptr;
-  uint32_t*  d_sf   = nullptr;
-  float2*    d_grid = nullptr;
-  float2*    d_ce   = nullptr;
-  float*     d_res  = nullptr;
-  uint32_t   cap    = 0;  // subframes
+  srsran_amd::PinBuf<uint32_t> h_sf{hipHostMallocMapped | hipHostMallocCoherent};
+  uint32_t*                    d_sf = nullptr;
+  srsran_amd::DevBuf<float2>   d_grid, d_ce;
+  srsran_amd::DevBuf<float>    d_res;
+  uint32_t   cap    = 0;  // subframes the four buffers are shaped for (0: release and rebuild)
   bool       cap_full = false;  // d_ce sized for full-grid (INTERPOLATE) estimates
   // what the channel-state feedback reads: the last batch's subframes in d_ce / d_res and their estimate form
   // (srsran_ue_dl_gpu_csi_batch), and whether a host-synchronous estimate was made (srsran_ue_dl_select_ri)
@@ -100,27 +100,28 @@ void select_mi(UeDlGpu* g, const srsran_cell_t& cell, const srsran_dl_sf_cfg_t* 
   }
 }
 
-bool grow(srsran_ue_dl_t* q, UeDlGpu* g, uint32_t nsf, bool full)
+// the device idle, then the batch buffers released (their shapes depend on the cell and the estimate form)
+void release_batch(UeDlGpu* g)
+{
+  hipDeviceSynchronize();
+  g->h_sf.reset(), g->d_grid.reset(), g->d_ce.reset(), g->d_res.reset();
+  g->d_sf = nullptr;
+  g->cap  = 0;
+}
+
+bool reserve_batch(srsran_ue_dl_t* q, UeDlGpu* g, uint32_t nsf, bool full)
 {
   if (g->cap >= nsf && (g->cap_full || !full)) {
     return true;
   }
-  hipDeviceSynchronize();
-  hipHostFree(g->h_sf);
-  hipFree(g->d_grid);
-  hipFree(g->d_ce);
-  hipFree(g->d_res);
-  g->h_sf = nullptr, g->d_sf = nullptr, g->d_grid = nullptr, g->d_ce = nullptr, g->d_res = nullptr;
-  g->cap             = 0;
+  release_batch(g);
   const size_t nre   = 12 * (size_t)q->cell.nof_prb;
   const size_t nrx   = q->nof_rx_antennas;
   const size_t ports = q->cell.nof_ports;
-  if (hipHostMalloc((void**)&g->h_sf, kStageRing * nsf * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
+  if (!g->h_sf.reserve((size_t)kStageRing * nsf) ||
       hipHostGetDevicePointer((void**)&g->d_sf, g->h_sf, 0) != hipSuccess ||
-      hipMalloc((void**)&g->d_grid, nsf * nrx * 14 * nre * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_ce, nsf * ports * nrx * nre * (full ? 14 : 1) * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&g->d_res, nsf * 4 * sizeof(float)) != hipSuccess) {
+      !g->d_grid.reserve(nsf * nrx * 14 * nre) || !g->d_ce.reserve(nsf * ports * nrx * nre * (full ? 14 : 1)) ||
+      !g->d_res.reserve((size_t)nsf * 4)) {
     return false;
   }
   g->cap      = nsf;
@@ -206,10 +207,6 @@ void srsran_ue_dl_free(srsran_ue_dl_t* q)
   UeDlGpu* g = (UeDlGpu*)q->gpu;
   if (g) {
     hipDeviceSynchronize();
-    hipHostFree(g->h_sf);
-    hipFree(g->d_grid);
-    hipFree(g->d_ce);
-    hipFree(g->d_res);
     for (hipEvent_t e : g->staged) {
       if (e) {
         hipEventDestroy(e);
@@ -295,12 +292,7 @@ int srsran_ue_dl_set_cell(srsran_ue_dl_t* q, srsran_cell_t cell)
                  srsran_phich_set_cell(&g->phich, &g->regs, cell) == SRSRAN_SUCCESS;
   g->regs_set = &g->regs;
   g->nof_pending_ul = 0;  // ue_dl.c:189
-  hipDeviceSynchronize();
-  hipHostFree(g->h_sf);
-  hipFree(g->d_grid);
-  hipFree(g->d_ce);
-  hipFree(g->d_res);
-  g->h_sf = nullptr, g->d_sf = nullptr, g->d_grid = nullptr, g->d_ce = nullptr, g->d_res = nullptr;
+  release_batch(g);
   return SRSRAN_SUCCESS;
 }
 
@@ -443,7 +435,7 @@ static int decode_batch(srsran_ue_dl_t*              q,
   if (!srsran_amd::chest_batch_cfg_supported(&q->chest, &cfg->chest_cfg, full)) {  // before any batch is staged
     return SRSRAN_ERROR;
   }
-  if (!grow(q, g, nof_sf, full)) {
+  if (!reserve_batch(q, g, nof_sf, full)) {
     return SRSRAN_ERROR;
   }
   g->last_nsf  = nof_sf;
@@ -473,8 +465,8 @@ static int decode_batch(srsran_ue_dl_t*              q,
       for (uint32_t b = 0; b < nof_sf; b++) {
         h_sf[b] = (uint8_t)(sfs[b].tti % 10);
       }
-      if (srsran_amd::chest_dl_gpu_estimate_batch_inline(&q->chest, &cfg->chest_cfg, h_sf, jobs, nof_sf, (const cf_t*)g->d_grid,
-                                                         nrx * rows * nre, (cf_t*)g->d_ce,
+      if (srsran_amd::chest_dl_gpu_estimate_batch_inline(&q->chest, &cfg->chest_cfg, h_sf, jobs, nof_sf, (const cf_t*)g->d_grid.get(),
+                                                         nrx * rows * nre, (cf_t*)g->d_ce.get(),
                                                          np * nrx * nre * (full ? rows : 1), full ? 1 : 0, g->d_res,
                                                          stream)) {
         return SRSRAN_ERROR;
@@ -495,8 +487,8 @@ static int decode_batch(srsran_ue_dl_t*              q,
       for (uint32_t b = 0; b < nof_sf; b++) {
         h_sf[b] = sfs[b].tti % 10;
       }
-      if (srsran_chest_dl_gpu_estimate_batch_cfg(&q->chest, &cfg->chest_cfg, d_sf, nof_sf, (const cf_t*)g->d_grid,
-                                                 nrx * rows * nre, (cf_t*)g->d_ce, np * nrx * nre * (full ? rows : 1),
+      if (srsran_chest_dl_gpu_estimate_batch_cfg(&q->chest, &cfg->chest_cfg, d_sf, nof_sf, (const cf_t*)g->d_grid.get(),
+                                                 nrx * rows * nre, (cf_t*)g->d_ce.get(), np * nrx * nre * (full ? rows : 1),
                                                  full ? 1 : 0, g->d_res, stream)) {
         return SRSRAN_ERROR;
       }
@@ -520,8 +512,8 @@ static int decode_batch(srsran_ue_dl_t*              q,
   }
   if (srsran_amd::stage_side_copy() || !one_limit) {  // in line: OFDM, estimator, then the PDSCH batch
     if (srsran_amd::handoff(g->ho, s) != hipSuccess ||
-        (d16 ? srsran_ofdm_rx_gpu_sc16(&q->fft[0], d16, scale, (cf_t*)g->d_grid, (uint32_t)nrx, nof_sf, cfo, stream)
-                : srsran_ofdm_rx_gpu(&q->fft[0], d_samples, (cf_t*)g->d_grid, (uint32_t)nrx, nof_sf, cfo, stream)) ||
+        (d16 ? srsran_ofdm_rx_gpu_sc16(&q->fft[0], d16, scale, (cf_t*)g->d_grid.get(), (uint32_t)nrx, nof_sf, cfo, stream)
+                : srsran_ofdm_rx_gpu(&q->fft[0], d_samples, (cf_t*)g->d_grid.get(), (uint32_t)nrx, nof_sf, cfo, stream)) ||
         estimate(nullptr) != SRSRAN_SUCCESS) {
       return SRSRAN_ERROR;
     }
@@ -552,8 +544,8 @@ static int decode_batch(srsran_ue_dl_t*              q,
     }
   }
   if (!copies_ok || srsran_amd::handoff(g->ho, s) != hipSuccess ||
-      (d16 ? srsran_ofdm_rx_gpu_sc16(&q->fft[0], d16, scale, (cf_t*)g->d_grid, (uint32_t)nrx, nof_sf, cfo, stream)
-                : srsran_ofdm_rx_gpu(&q->fft[0], d_samples, (cf_t*)g->d_grid, (uint32_t)nrx, nof_sf, cfo, stream)) ||
+      (d16 ? srsran_ofdm_rx_gpu_sc16(&q->fft[0], d16, scale, (cf_t*)g->d_grid.get(), (uint32_t)nrx, nof_sf, cfo, stream)
+                : srsran_ofdm_rx_gpu(&q->fft[0], d_samples, (cf_t*)g->d_grid.get(), (uint32_t)nrx, nof_sf, cfo, stream)) ||
       estimate(&js) != SRSRAN_SUCCESS) {
     for (uint32_t i = 0; i < js.n; i++) {  // the fused ones did not run: their fences must come as well
       srsran_amd::stage_copy_job(js.job[i], s);

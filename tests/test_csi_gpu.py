@@ -260,6 +260,17 @@ def test_noise_bound(env):
         assert r.tobytes() == recs[0].tobytes()
 
 
+def test_host_rows_scratch_regrowth_is_bit_identical(env):
+    """the process-wide scratch of the host-row calls: the smallest sample set, a larger one (the scratch is
+    reallocated), the smallest again -- the two small records are the same bytes, and so are the two large ones"""
+    U, torch, refs = env
+    small, large = channel(21, 192), channel(22, 16800 + 2400)
+    recs = [U.precoding_csi_2x2(h, 0.05) for h in (small, large, small, large)]
+    assert all(r[0] == 0 for r in recs)
+    assert recs[0][1].tobytes() == recs[2][1].tobytes() and recs[1][1].tobytes() == recs[3][1].tobytes()
+    assert recs[0][1].tobytes() != recs[1][1].tobytes()
+
+
 def test_rank_deficient_channel(env):
     """both ports' columns equal: ri_cn = 0 and every output finite"""
     U, torch, refs = env

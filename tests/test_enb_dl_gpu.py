@@ -193,3 +193,46 @@ def test_re_table_cache_wrap_in_and_across_batches(gpu):
         sb.free()
     ue.free()
     enb.free()
+
+
+def test_tx_batch_regrowth_is_bit_identical(gpu):
+    """One eNB DL object: a one-subframe batch of the smallest grant, a four-subframe batch of C3 grants (more
+    grid, e-bit, item and subframe-index scratch), the first batch again -- samples equal a fresh object's."""
+    torch = gpu
+    from srsran_4g_amd import enb_dl as E
+    from srsran_4g_amd import ue_dl as U
+    nprb, P, cell_id, rnti = 100, 2, 11, 0x1234
+    U.use_standard_symbol_size(True)
+    N = SY.symbol_sz(nprb)
+    sf_len = 2 * (7 * N + 160 * N // 2048 + 6 * (144 * N // 2048))
+    rng = np.random.default_rng(15)
+    cell = U.cell(nprb, P, cell_id)
+    keep = []
+
+    def batch(grants):  # [(tti, cfi, scheme, ntb, Qm, tbs)]
+        sfs = []
+        for tti, cfi, scheme, ntb, Qm, tbs in grants:
+            nre = int(SY.pdsch_mask(nprb, P, cell_id, cfi, tti % 10).sum())
+            d = [torch.from_numpy(rng.integers(0, 256, tbs // 8, dtype=np.uint8)).cuda() for _ in range(ntb)]
+            cfg = U.pdsch_cfg(nprb, nre, [tbs] * ntb, [Qm] * ntb, scheme=scheme, rnti=rnti)
+            keep.extend(d + [cfg])
+            sfs.append((tti, cfi, cfg, [x.data_ptr() for x in d]))
+        return sfs
+
+    small = batch([(7, 3, "diversity", 1, 2, 2216)])
+    large = batch([(t, 1, "cdd", 2, 6, 75376) for t in (1, 2, 3, 4)])
+
+    def run(enb, sfs):
+        d_tx = torch.zeros((len(sfs), P, sf_len, 2), dtype=torch.float32, device="cuda")
+        assert enb.tx_batch(sfs, d_tx.data_ptr()) == 0
+        torch.cuda.synchronize()
+        return d_tx.cpu().numpy()
+
+    one = E.EnbDl(cell)
+    for step, sfs in enumerate((small, large, small)):
+        fresh = E.EnbDl(cell)
+        want = run(fresh, sfs)
+        fresh.free()
+        got = run(one, sfs)
+        assert np.abs(got).max() > 0 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), step
+    one.free()

@@ -104,6 +104,40 @@ def test_encode_batch_and_round_trip(env):
             sb.free()
 
 
+def test_encode_scratch_regrowth_is_bit_identical(env):
+    """One object: the smallest TB, a batch that needs more encoder scratch, the smallest again -- sync and batch
+    outputs equal a fresh object's."""
+    import torch
+    S, _, ora = env
+    rng = np.random.default_rng(19)
+    small, large = [(104, 2, 288, 0)], [(75376, 6, 86400, 0), (30576, 6, 39600, 2), (75376, 6, 86400, 1)]
+
+    def run(q, cases, payloads):
+        tbs, Qm, G, rv = cases[0]
+        ret, e = q.encode(tbs, Qm, rv, G, payloads[0])
+        assert ret == 0
+        ents, keep = [], []
+        for (tbs, Qm, G, rv), p in zip(cases, payloads):
+            d_in = torch.from_numpy(p).cuda()
+            d_out = torch.zeros((G + 7) // 8, dtype=torch.uint8, device="cuda")
+            keep += [d_in, d_out]
+            ents.append((tbs, Qm, rv, G, d_in.data_ptr(), d_out.data_ptr()))
+        assert q.encode_batch(ents) == 0
+        torch.cuda.synchronize()
+        return [e.copy()] + [d.cpu().numpy() for d in keep[1::2]]
+
+    one = S.Sch()
+    for cases in (small, large, small):
+        payloads = [rng.integers(0, 256, c[0] // 8, dtype=np.uint8) for c in cases]
+        fresh = S.Sch()
+        want = run(fresh, cases, payloads)
+        fresh.free()
+        got = run(one, cases, payloads)
+        assert all(np.array_equal(g, w) for g, w in zip(got, want)), cases
+        assert np.array_equal(got[1], _want(ora, cases[0][0], cases[0][1], cases[0][3], cases[0][2], payloads[0]))
+    one.free()
+
+
 def test_encode_refusals(env):
     S, q, ora = env
     ret, _ = q.encode(1000, 2, 0, 2000, np.zeros(125, np.uint8))  # 1000 + 24 needs filler bits

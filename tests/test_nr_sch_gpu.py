@@ -267,3 +267,34 @@ def test_prb_mcs_rv_sweep_noise_free(ora, q, n_prb):
             if rv == 0:
                 assert crc and np.array_equal(got, pl), (n_prb, Qm, r1024, tbs)
             sb.free()
+
+
+def test_scratch_regrowth_is_bit_identical(ora):
+    """One NR SCH object: the smallest TB, the largest (more descriptor, iteration, LLR and payload scratch; a
+    larger pinned descriptor stage), the smallest again -- equal to a fresh object's results."""
+    rng = np.random.default_rng(33)
+
+    def tb(n_re, R, Qm):
+        tbs, G = _tbs(n_re, R, Qm, 1), n_re * Qm
+        t = S.tb_info(tbs, R, Qm, G, 1, nof_prb=273, mcs256=Qm == 8)
+        pl = rng.integers(0, 256, tbs // 8).astype(np.uint8)
+        e = NrCodeblocks(t, pl).rate_match(0)
+        return tbs, R, Qm, G, pl, np.where(e == 1, -20, 20).astype(np.int8)
+
+    small, large = tb(100, 0.2, 2), tb(12 * 13 * 273, 0.93, 8)
+
+    def run(s, c):
+        tbs, R, Qm, G, pl, llr = c
+        sb = S.nr_softbuffer()
+        ret, crc, avg, got = s.decode(sb, tbs, R, Qm, G, 1, 0, llr, mcs256=Qm == 8)
+        sb.free()
+        assert ret == 0 and crc and np.array_equal(got, pl)
+        return [np.float64(avg), got]
+
+    one = S.SchNr(nof_prb=273, max_nof_iter=6)
+    for c in (small, large, small):
+        fresh = S.SchNr(nof_prb=273, max_nof_iter=6)
+        want = run(fresh, c)
+        fresh.free()
+        assert all(np.array_equal(g, w) for g, w in zip(run(one, c), want)), c[0]
+    one.free()

@@ -62,6 +62,26 @@ def test_ofdm_rx_matches_numpy(U, nof_prb):
     rx.free()
 
 
+@pytest.mark.parametrize("tx", [False, True])
+def test_ofdm_staging_regrowth_is_bit_identical(U, tx):
+    """One 100-PRB object resized to 6 PRB, back to 100 (larger input / output staging), to 6 again: each host
+    transform equal to a fresh object's of that size."""
+    import ctypes
+    rng = np.random.default_rng(3 + tx)
+    one = U.OfdmRx(100, tx=tx)
+    data = {}
+    for nof_prb in (6, 100, 6):
+        assert U.lib().srsran_ofdm_rx_set_prb(ctypes.byref(one.q), 0, nof_prb) == 0
+        fresh = U.OfdmRx(nof_prb, tx=tx)
+        n = 14 * 12 * nof_prb if tx else ofdm_np.sf_len(fresh.symbol_sz)
+        x = data.setdefault(nof_prb, (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64))
+        want = fresh.tx(x) if tx else fresh.rx(x)
+        got = one.tx(x) if tx else one.rx(x)
+        fresh.free()
+        assert np.abs(got).max() > 0 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), nof_prb
+    one.free()
+
+
 def test_ofdm_normalize(U):
     rng = np.random.default_rng(1)
     rx = U.OfdmRx(100, normalize=True)

@@ -216,6 +216,54 @@ def test_batch_is_bit_identical_to_single_calls(golden):
                     assert not r["payload"].any() and r["nof_tx_ports"] == 0 and r["sfn_offset"] == 0, n
 
 
+def test_batch_descriptor_regrowth_is_bit_identical(golden):
+    """One object as the first entry (the owner of the batch's descriptors) of a one-entry batch, a four-entry batch
+    (its descriptor buffer is reallocated) and a one-entry batch again.  A second set of objects takes the same
+    calls behind a new first entry every time, so none of them ever owns descriptors: results and histories of the
+    two sets are the same bits."""
+    z, metas, _ = golden
+    names = ["comb3_2p", "p6_id0_1p", "p15_id1_4p_ext", "search_2p"]  # the owner has three recorded calls
+    ncalls = [len(metas[n]["calls"]) for n in names]
+
+    def make(n):
+        c = C.by_name(n)
+        grids, ce = expand(c, z)
+        _, _, sf_re, _ = geometry(c)
+        d_grid = torch.from_numpy(grids.view(np.float32).reshape(grids.shape[0], -1)).cuda()
+        d_ce = torch.from_numpy(np.ascontiguousarray(ce[:, None]).view(np.float32)).cuda()
+        d_noise = torch.tensor([k["noise"] for k in metas[n]["calls"]], dtype=torch.float32, device="cuda")
+        return dict(o=B.Pbch(cell_of(c)), g=d_grid, ce=d_ce, row=sf_re, noise=d_noise, i=0, n=n)
+
+    def entry(x):
+        i = min(x["i"], x["g"].shape[0] - 1)
+        x["i"] += 1
+        return x["o"].entry(x["g"][i].data_ptr(), x["ce"].data_ptr(), x["row"], 1, x["noise"][i:].data_ptr())
+
+    def batch(objs):
+        ents = [entry(x) for x in objs]
+        d_out = torch.zeros(len(ents) * B.RES_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        assert B.decode_batch(ents, d_out.data_ptr()) == 0
+        torch.cuda.synchronize()
+        return d_out.cpu().numpy().view(B.RES_DTYPE)
+
+    live, ref, extra = [make(n) for n in names], [make(n) for n in names], []
+    assert ncalls[0] >= 3
+    found = 0
+    for sel in ([0], [0, 1, 2, 3], [0]):
+        got = batch([live[j] for j in sel])
+        extra.append(make(names[1]))
+        want = batch([extra[-1]] + [ref[j] for j in sel])[1:]
+        assert got.tobytes() == want.tobytes(), sel
+        found += int(got["found"].sum())
+    assert found > 0
+    for a, b in zip(live, ref):
+        (h, fi), (bh, bfi) = a["o"].last_llr(), b["o"].last_llr()
+        assert fi == bfi and np.array_equal(h.view(np.uint32), bh.view(np.uint32)), a["n"]
+    for x in live + ref + extra:
+        x["o"].free()
+
+
 def test_batch_refuses_bad_entries():
     pb = B.Pbch(U.cell(6, 1, 0))
     d = torch.zeros(4096, dtype=torch.float32, device="cuda")

@@ -191,6 +191,39 @@ def test_pure_noise_candidates_bit_exact(mods):
         ctl.free()
 
 
+def test_candidate_buffers_regrowth_is_bit_identical(mods):
+    """One control object: one candidate, every candidate of the region (larger candidate, result and pinned
+    read-back buffers), one candidate again -- equal to a fresh object's decode of the same LLRs."""
+    PD, U = mods
+    rng = np.random.default_rng(4)
+    nprb, nports, cid, tti, cfi = 50, 2, 9, 2, 3
+
+    def make():
+        ctl = PD.Control(PD.cell(nprb, nports, cid), 2)
+        if not hasattr(make, "llr"):
+            make.llr = (rng.standard_normal(72 * ctl.ncce(cfi)) * 2).astype(np.float32)
+        ctl.set_llr(cfi, make.llr)
+        return ctl
+
+    one = make()
+    nof_cce = one.ncce(cfi)
+    every = [(L, n, f) for L in range(4) for n in range(0, nof_cce - (1 << L) + 1, 1 << L)
+             for f in (P.FORMAT1A, P.FORMAT2A)]
+    assert len(every) > 64
+    try:
+        for fl in (every[:1], every, every[:1]):
+            fresh = make()
+            try:
+                want = fresh.decode(tti, cfi, fl)
+            finally:
+                fresh.free()
+            got = one.decode(tti, cfi, fl)
+            for g, w in zip(got, want):
+                assert g[0] == w[0] and np.array_equal(g[1], w[1]) and g[2:] == w[2:], len(fl)
+    finally:
+        one.free()
+
+
 def test_find_dl_dci_and_pdsch_without_injected_grant(mods):
     """C3 (100 PRB, 2x2 TM3, 64QAM, 2 TBs): time samples -> OFDM -> CRS estimate -> PCFICH (CFI from
     the air) -> PDCCH blind search (format 2A for the C-RNTI) -> grant -> PDSCH decode; payloads equal"""

@@ -8,6 +8,7 @@ Chain tier: GPU OFDM + channel estimation differ from numpy / the oracle by floa
 (FFT and reductions in another order; FFT parity is unpinned), so the full GPU chain
 is checked by decoding (CRC pass, payload == transmitted) and by agreement with the oracle chain.
 """
+import ctypes
 import json
 import os
 
@@ -118,6 +119,36 @@ def test_pdsch_decode_bitexact(U, SCH, ora, case, opts):
         if not fail:
             assert crc and np.array_equal(payload[: tbs[q] // 8], pls[q])
     pd.free()
+
+
+def test_pdsch_work_area_regrowth_is_bit_identical(U, SCH, ora):
+    """One PDSCH object: the 6-PRB grant (grids and work area under the 64 KB floor), the 100-PRB C3 grant (both
+    above it), the 6-PRB grant again -- every result equal to a fresh object's on the same input."""
+    rng = np.random.default_rng(55)
+    small = dict(nof_prb=6, cell_id=2, tbs=(1800, 1800), Qm=(4, 4), cfi=2, tti=7)
+    large = dict(nof_prb=100, cell_id=1, tbs=(TBS, TBS), Qm=(6, 6), cfi=1, tti=1)
+    data = {id(k): _case(ora, rng, **k) for k in (small, large)}
+
+    def run(pd, k):
+        pls, x, nre, grids, ce, st = data[id(k)]
+        sbs = [SCH.SoftbufferRx(nof_prb=k["nof_prb"]) for _ in k["tbs"]]
+        cfg = U.pdsch_cfg(k["nof_prb"], nre, k["tbs"], k["Qm"], softbuffers=sbs)
+        ret, out = pd.decode(cfg, k["tti"], k["cfi"], grids, ce, st["noise"])
+        assert ret == 0
+        for q, (crc, payload, avg) in enumerate(out):
+            assert crc and np.array_equal(payload[: k["tbs"][q] // 8], pls[q])
+        return [np.concatenate([[crc, avg], payload]) for crc, payload, avg in out]
+
+    one = U.Pdsch(U.cell(100, 2, 1), 2)
+    for k in (small, large, small):
+        c = U.cell(k["nof_prb"], 2, k["cell_id"])
+        assert U.lib().srsran_pdsch_set_cell(ctypes.byref(one.q), c) == 0
+        fresh = U.Pdsch(c, 2)
+        want = run(fresh, k)
+        fresh.free()
+        got = run(one, k)
+        assert all(np.array_equal(g, w) for g, w in zip(got, want)), k["nof_prb"]
+    one.free()
 
 
 def test_pdsch_already_acked_is_skipped(U, SCH, ora):

@@ -172,6 +172,36 @@ def test_encode_batch_of_subframes_equals_single_calls(mods, c):
         o.free()
 
 
+def test_item_buffers_regrowth_is_bit_identical(mods):
+    """One object: a one-item batch, a batch of every resource of two subframes (larger item and unit buffers), the
+    one-item batch again -- grids equal a fresh object's bit for bit."""
+    torch = mods[0]
+    c = next(x for x in SENT if x["name"] == "p100_ng2_1p")
+    rng = np.random.default_rng(12)
+    every = [(b, c["tti"] + 4 * b, g, s, int(rng.integers(0, 2))) for b in range(2) for g in range(c["ngroups"])
+             for s in range(8)]
+
+    def run(o, batch):
+        nsf = 1 + max(x[0] for x in batch)
+        d = torch.zeros((nsf, c["ports"], sf_re(c), 2), dtype=torch.float32, device="cuda")
+        assert o.ph.encode_batch(batch, nsf, d.data_ptr()) == 0
+        torch.cuda.synchronize()
+        return to_host(d, (nsf, c["ports"], sf_re(c)))
+
+    one = Obj(mods, c)
+    try:
+        for batch in (every[:1], every, every[:1]):
+            fresh = Obj(mods, c)
+            try:
+                want = run(fresh, batch)
+            finally:
+                fresh.free()
+            got = run(one, batch)
+            assert np.count_nonzero(want) > 0 and np.array_equal(bits(got), bits(want)), len(batch)
+    finally:
+        one.free()
+
+
 @pytest.mark.parametrize("c", ENB, ids=ids(ENB))
 def test_enb_tx_batch_with_phich(mods, c):
     torch, PD, _, E, U = mods

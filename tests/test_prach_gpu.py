@@ -250,6 +250,30 @@ def test_batch_equals_singles_in_any_order(cells):
             assert r.tobytes() == singles[i][3].tobytes() and np.array_equal(o, singles[i][4])
 
 
+def test_batch_workspace_regrowth_is_bit_identical():
+    """One object as a batch's first: one occasion, twenty (above the 16-occasion floor, so the pinned and device
+    workspace is reallocated), one again -- results equal a fresh object's bit for bit."""
+    a = Cell(6, 0, 0, 1)
+    x = [R.channel(a.ref, [((7 * k + 3) % 64, 1.0, k % 5)], 0, -10.0, 40 + k) for k in range(20)]
+    dev = [torch.from_numpy(v.view(np.float32)).cuda() for v in x]
+    a.p.set_detect_factor(FACTOR)
+    try:
+        for n in (1, 20, 1):
+            fresh = Cell(6, 0, 0, 1)
+            fresh.p.set_detect_factor(FACTOR)
+            try:
+                ret, want, _ = P.detect_batch([(fresh.p, 0, dev[i].data_ptr(), len(x[i])) for i in range(n)])
+                assert ret == 0
+            finally:
+                fresh.free()
+            ret, got, _ = P.detect_batch([(a.p, 0, dev[i].data_ptr(), len(x[i])) for i in range(n)])
+            assert ret == 0 and len(got) == n
+            for g, w in zip(got, want):
+                assert len(g[0]) >= 1 and all(u.tobytes() == v.tobytes() for u, v in zip(g, w)), n
+    finally:
+        a.free()
+
+
 def test_batch_refuses_a_short_entry_and_writes_nothing(cells):
     a, b = cells(6, 0, 0, 1), cells(25, 16, 837, 5)
     xa = torch.from_numpy(R.channel(a.ref, [(3, 1.0, 0)], 0, -10.0, 1).view(np.float32)).cuda()

@@ -300,3 +300,67 @@ def test_pusch_batch_matches_sync(env, mixed):
     for k in keep:
         if hasattr(k, "free"):
             k.free()
+
+
+def test_pusch_scratch_regrowth_is_bit_identical(env):
+    """One estimator and one PUSCH object of a 100-PRB cell: a 1-PRB grant, then a 100-PRB grant and a 3-UE batch
+    (more of every growable buffer), then the 1-PRB grant again -- the host-synchronous decode and the batch both
+    equal fresh objects' results on the same grids."""
+    import torch
+
+    from srsran_4g_amd import pusch as P
+    from srsran_4g_amd import sch as S
+    cell_id, cprb, dcfg = 29, 100, (7, 29, True, False)
+    cell, d = _setup(cell_id, cprb, 0, dcfg)
+    rng = np.random.default_rng(61)
+    sbs = []
+
+    def ue(Qm, L, n0, tbs, tti):
+        sf = P.srsran_ul_sf_cfg_t()
+        sf.tti = tti
+        def mk():  # a configuration with a soft buffer of its own, kept alive until the test ends
+            sbs.append(S.SoftbufferRx(nof_prb=100))
+            return TX.make_cfg(cprb, Qm, L, n0, tbs, 0, 0, None, softbuffer=sbs[-1])
+        grid = TX.pusch_subframe(env, cell_id, cprb, 0, mk(), d, tti, rng, snr_db=35.0)[0]
+        return sf, mk, grid, tbs, slice(12 * n0, 12 * (n0 + L))
+
+    small, large = ue(2, 1, 2, 104, 0), ue(6, 100, 0, 61664, 2)
+
+    def run(ch, pu, ues):
+        sf, mk, grid, tbs, cols = ues[0]
+        cfg = mk()
+        assert ch.estimate(sf, cfg, grid) == 0
+        ret, o, data = pu.decode(sf, cfg, ch.res, grid, tbs // 8)
+        assert ret == 0
+        out = [np.array([o.crc, o.avg_iterations_block, ch.res.noise_estimate, ch.res.epre]), data.copy(),
+               ch.ce(grid.size).reshape(grid.shape)[:, cols].copy()]  # the estimator writes the grant's REs only
+        n = len(ues)
+        arr, res, cres = (P.srsran_pusch_gpu_ue_t * n)(), (P.srsran_pusch_res_t * n)(), (P.srsran_chest_ul_res_t * n)()
+        keep = []
+        for i, (sf, mk, grid, tbs, _) in enumerate(ues):
+            cfg = mk()
+            d_grid = torch.from_numpy(grid.view(np.float32).reshape(-1).copy()).cuda()
+            data_b = np.zeros(tbs // 8 + 64, np.uint8)
+            keep += [cfg, d_grid, data_b]
+            arr[i].chest, arr[i].sf, arr[i].cfg = ctypes.pointer(ch.q), ctypes.pointer(sf), ctypes.pointer(cfg)
+            arr[i].d_sf_symbols = d_grid.data_ptr()
+            res[i].data = data_b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        assert P.lib().srsran_pusch_gpu_decode_batch(ctypes.byref(pu.q), n, arr, cres, res) == 0
+        for i in range(n):
+            out += [np.array([res[i].crc, res[i].avg_iterations_block, cres[i].noise_estimate, cres[i].epre]), keep[3 * i + 2]]
+        return out
+
+    ch1, pu1 = P.ChestUl(cell, d), P.Pusch(cell)
+    for step, ues in enumerate(([small], [large, small, large], [small])):
+        ch0, pu0 = P.ChestUl(cell, d), P.Pusch(cell)
+        want = run(ch0, pu0, ues)
+        pu0.free()
+        ch0.free()
+        got = run(ch1, pu1, ues)
+        assert len(got) == len(want), step
+        assert not [i for i, (g, w) in enumerate(zip(got, want)) if not np.array_equal(g, w)], step
+        assert len(ues) > 1 or got[0][0] == 1, step  # the QPSK 1-PRB TB decodes at this SNR
+    pu1.free()
+    ch1.free()
+    for sb in sbs:
+        sb.free()

@@ -189,6 +189,68 @@ def test_random_small_grants(env):
         done += 1
 
 
+def test_scratch_regrowth_is_bit_identical(env, models):
+    """One UL-SCH object and one ue_ul object: the smallest case, then a call that needs more of every growable
+    buffer (the 25-PRB, 2-code-block grants; a batch of every 25-PRB case), then the smallest again -- bits,
+    samples and grids equal a fresh object's."""
+    import torch
+
+    from srsran_4g_amd import sch as S
+    from srsran_4g_amd import ue_ul as UL
+    by = TC.BY_NAME
+
+    def enc(sch, c):
+        cell, d, sf, cfg = TC.make(c)
+        _limited(c, cfg)
+        _, payload, u = models[c["name"]]
+        ret, g, q = UL.ulsch_encode(sch, cfg, payload if cfg.grant.tb.tbs else None, u)
+        return [np.int64(ret), g.copy(), q.copy()]
+
+    one = S.Sch()
+    for name in ("t1", "t9", "t8", "t1"):
+        fresh = S.Sch()
+        want = enc(fresh, by[name])
+        fresh.free()
+        assert all(np.array_equal(g, w) for g, w in zip(enc(one, by[name]), want)), name
+    one.free()
+
+    cell25 = TC.make(by["t11a"])[0]
+    names25 = [c["name"] for c in TC.CASES if (c["nof_prb"], c["cp"]) == (25, 0)]
+    assert len(names25) > 3
+
+    def tx(ue, names):
+        keep, ents, outs = [], [], []
+        for i, name in enumerate(names):
+            c = by[name]
+            m, payload, u = models[name]
+            cell, d, sf, cfg = TC.make(c)
+            ucfg = TC.ue_cfg(c, cfg, d, mode=i % 2, peak=0.7, cfo=1.3e-1 if c["L"] % 2 else None)
+            d_pl = torch.from_numpy(np.concatenate([payload, np.zeros(16, np.uint8)])).cuda()
+            d_out = torch.zeros(2 * ue.sf_len, dtype=torch.float32, device="cuda")
+            d_grid = torch.zeros(2 * 2 * m["nsym"] * 12 * c["nof_prb"], dtype=torch.float32, device="cuda")
+            keep.extend([d_pl, ucfg, sf, u, cfg, d])
+            outs += [d_out, d_grid]
+            ents.append((ue, sf, ucfg, u, d_pl.data_ptr() if cfg.grant.tb.tbs else None, d_out.data_ptr(),
+                         d_grid.data_ptr()))
+        assert UL.tx_batch(ents) == 0
+        torch.cuda.synchronize()
+        return [o.cpu().numpy() for o in outs]
+
+    ue = UL.UeUl(cell25)
+    try:
+        for names in (["t11a"], names25, ["t11a"]):
+            fresh = UL.UeUl(cell25)
+            try:
+                want = tx(fresh, names)
+            finally:
+                fresh.free()
+            got = tx(ue, names)
+            assert np.abs(got[0]).max() > 0
+            assert all(np.array_equal(g, w) for g, w in zip(got, want)), names
+    finally:
+        ue.free()
+
+
 def test_batch_bit_identical_to_single_calls(env, models):
     """all cases in one batch, two orders, two compositions; samples and grids equal the single calls bit for bit"""
     import torch

@@ -286,6 +286,50 @@ def test_dlsch_batch_new_data_and_harq(S, q, ora):
                 assert not sb.read_cb(cb, S.SOFTBUFFER_SIZE).any(), (label, cb)
 
 
+def test_dlsch_scratch_regrowth_is_bit_identical(S, ora):
+    """One DL-SCH object: the smallest TB, then a call that needs more of every growable buffer (sync: the e-bit
+    scratch; batch: 6 x 13 code blocks > the 64-slot floor and their descriptors > the 4096-byte staging floor),
+    then the smallest again -- sync and batch results equal a fresh object's on the same input."""
+    rng = np.random.default_rng(41)
+
+    def tb_case(tbs, Qm, G, sigma):
+        tb = rng.integers(0, 256, tbs // 8, dtype=np.uint8)
+        return tbs, Qm, llrs(ora, tbs, Qm, 0, G, tb, sigma, rng)
+
+    small, large = [tb_case(16, 2, 240, 0)], [tb_case(75376, 6, 86400, 0.45) for _ in range(6)]
+
+    def run(q, tbs_list):
+        q.set_max_noi(8)
+        tbs, Qm, llr = tbs_list[0]
+        ret, data, avg = q.decode(S.SoftbufferRx(nof_prb=100), tbs, Qm, 0, llr)
+        out = [np.int64(ret), data.copy(), np.float64(avg)]
+        keep, entries = [], []
+        for tbs, Qm, llr in tbs_list:
+            d_e = torch.from_numpy(llr).cuda()
+            d_data = torch.zeros(tbs // 8 + 64, dtype=torch.uint8, device="cuda")
+            sb = S.SoftbufferRx(nof_prb=100)
+            keep += [d_e, d_data, sb]
+            entries.append((tbs, Qm, 0, len(llr), d_e.data_ptr(), d_data.data_ptr(), sb))
+        d_res = torch.full((len(entries),), 77, dtype=torch.int32, device="cuda")
+        d_avg = torch.zeros(len(entries), dtype=torch.float32, device="cuda")
+        assert q.decode_batch(entries, d_res.data_ptr(), d_avg.data_ptr()) == 0
+        torch.cuda.synchronize()
+        out += [d_res.cpu().numpy(), d_avg.cpu().numpy()] + [keep[3 * i + 1].cpu().numpy() for i in range(len(entries))]
+        for sb in keep[2::3]:
+            sb.free()
+        return out
+
+    one = S.Sch()
+    for step, tbs_list in enumerate((small, large, small)):
+        fresh = S.Sch()
+        want = run(fresh, tbs_list)
+        fresh.free()
+        got = run(one, tbs_list)
+        assert len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want)), step
+        assert got[0] == ora.dlsch_decode(tbs_list[0][0], tbs_list[0][1], 0, tbs_list[0][2], 8)[0], step
+    one.free()
+
+
 def test_rm_rx_long_e(S, ora):
     """E > 65535 on one code block (repetition over many circular-buffer periods)."""
     rng = np.random.default_rng(4)

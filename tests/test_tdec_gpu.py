@@ -121,6 +121,29 @@ def test_ragged_batches(ora, dec, ncb):
         assert np.array_equal(got, ora.run_batch(K, llr, True, 6))
 
 
+def test_scratch_regrowth_is_bit_identical(ora):
+    """One object: smallest call, a call that needs more of the batch input / output and iteration-state
+    scratch, the smallest call again -- each equal to a fresh object's result on the same input."""
+    rng = np.random.default_rng(77)
+    small, large = _inputs(ora, 40, rng, 2, True)[:1], _inputs(ora, 6144, rng, 8, True)
+
+    def run(d, llr, K):
+        out = [d.run_all_batch(llr, 4, K)]
+        assert d.new_cb(K) == 0
+        out += [d.iteration(llr[0]).copy() for _ in range(3)]
+        return out
+
+    one = tdec.TurboDecoder()
+    for llr, K in ((small, 40), (large, 6144), (small, 40)):
+        fresh = tdec.TurboDecoder()
+        want = run(fresh, llr, K)
+        fresh.free()
+        got = run(one, llr, K)
+        assert all(np.array_equal(g, w) for g, w in zip(got, want)), K
+        assert np.array_equal(got[0], ora.run_batch(K, llr, True, 4))
+    one.free()
+
+
 def test_empty_batch(dec):
     llr = np.zeros((0, tdec.input_len(6144, True)), np.int16)
     assert dec.run_all_batch(llr, 8, 6144).shape == (0, 768)

@@ -107,3 +107,56 @@ def test_ulsch_batch_matches_oracle(ora):
         if isinstance(k, S.SoftbufferRx):
             k.free()
     q.free()
+
+
+@pytest.mark.gpu
+def test_ulsch_scratch_regrowth_is_bit_identical(ora):
+    """One object: the smallest case, then calls that need more of every growable buffer (sync: the q / g
+    scratch; batch: 66 TBs > the 64-descriptor floor), then the smallest again -- equal to a fresh object's."""
+    import torch
+
+    from srsran_4g_amd import sch as S
+    rng = np.random.default_rng(91)
+
+    def case(Qm, L, nsymb, tbs):
+        nb = L * 12 * nsymb * Qm
+        payload = rng.integers(0, 256, tbs // 8, dtype=np.uint8)
+        return tbs, Qm, nb, nsymb, _ul_llrs(ora, tbs, Qm, 0, nb, payload, 0.3, rng, nsymb)[1]
+
+    small = [case(2, 1, 12, 56)]
+    large = [case(4, 100, 12, 51024)] + [case(2, 1, 12, 56) for _ in range(65)]
+
+    def run(q, cases):
+        q.set_max_noi(8)
+        tbs, Qm, nb, nsymb, qb = cases[0]
+        sb = S.SoftbufferRx(nof_prb=100)
+        ret, data, g, avg, _ = q.ulsch_decode(sb, tbs, Qm, 0, nsymb, qb)
+        sb.free()
+        out = [np.int64(ret), data.copy(), g.copy(), np.float64(avg)]
+        entries, keep = [], []
+        for tbs, Qm, nb, nsymb, qb in cases:
+            d_q = torch.from_numpy(qb).cuda()
+            d_g = torch.zeros(nb, dtype=torch.int16, device="cuda")
+            d_d = torch.zeros(tbs // 8 + 64, dtype=torch.uint8, device="cuda")
+            sb = S.SoftbufferRx(nof_prb=100)
+            keep += [d_q, d_g, d_d, sb]
+            entries.append((tbs, Qm, 0, nb, nsymb, d_q.data_ptr(), d_g.data_ptr(), d_d.data_ptr(), sb, 1))
+        d_res = torch.full((len(entries),), 77, dtype=torch.int32, device="cuda")
+        d_avg = torch.zeros(len(entries), dtype=torch.float32, device="cuda")
+        assert q.ulsch_decode_batch(entries, d_res.data_ptr(), d_avg.data_ptr()) == 0
+        torch.cuda.synchronize()
+        out += [d_res.cpu().numpy(), d_avg.cpu().numpy()]
+        out += [k.cpu().numpy() for i, k in enumerate(keep) if i % 4 in (1, 2)]
+        for sb in keep[3::4]:
+            sb.free()
+        return out
+
+    one = S.Sch()
+    for step, cases in enumerate((small, large, small)):
+        fresh = S.Sch()
+        want = run(fresh, cases)
+        fresh.free()
+        got = run(one, cases)
+        assert len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want)), step
+        assert got[0] == 0 and not got[4].any(), step
+    one.free()

@@ -6,7 +6,7 @@
  *   srsran_refsignal_dmrs_pusch_cfg_t / srsran_refsignal_dmrs_pusch_gen
  *                                     lib/include/srsran/phy/ch_estimation/refsignal_ul.h:46-51, 114-119
  *   srsran_chest_ul_t / _res_t, srsran_chest_ul_init / free / res_init / res_free / res_set_identity /
- *   set_cell / pregen / estimate_pusch  lib/include/srsran/phy/ch_estimation/chest_ul.h:40-125
+ *   set_cell / pregen / estimate_pusch / estimate_srs  lib/include/srsran/phy/ch_estimation/chest_ul.h:40-125
  *   srsran_dft_precoding_valid_prb / get_valid_prb   lib/include/srsran/phy/dft/dft_precoding.h:47-49
  *   srsran_pusch_t, srsran_pusch_res_t, srsran_pusch_init_enb / free / set_cell / assert_grant /
  *   decode                            lib/include/srsran/phy/phch/pusch.h:43-110
@@ -69,6 +69,22 @@ uint32_t srsran_dft_precoding_get_valid_prb(uint32_t nof_prb);
  * asynchronous on `stream` (hipStream_t, NULL = default stream).  d_input / d_output: device. */
 int srsran_dft_precoding_gpu(const cf_t* d_input, cf_t* d_output, uint32_t nof_prb, uint32_t nof_symbols, void* stream);
 
+/* SRS configuration (refsignal_ul.h:53-70) */
+typedef struct {
+  uint32_t subframe_config;
+  uint32_t bw_cfg;
+  bool     simul_ack;
+  uint32_t B;
+  uint32_t b_hop;
+  uint32_t n_srs;
+  uint32_t I_srs;
+  uint32_t k_tc;
+  uint32_t n_rrc;
+  bool     dedicated_enabled;
+  bool     common_enabled;
+  bool     configured;
+} srsran_refsignal_srs_cfg_t;
+
 typedef struct {
   cf_t*    ce; /* host, nof_re = nof_prb * 12 * 2 * N_symb(cp) */
   uint32_t nof_re;
@@ -100,7 +116,10 @@ int  srsran_chest_ul_res_init(srsran_chest_ul_res_t* q, uint32_t max_prb);
 void srsran_chest_ul_res_set_identity(srsran_chest_ul_res_t* q);
 void srsran_chest_ul_res_free(srsran_chest_ul_res_t* q);
 int  srsran_chest_ul_set_cell(srsran_chest_ul_t* q, srsran_cell_t cell);
-/* srs_cfg: SRS is not provided; pass NULL (a non-NULL srs_cfg is ignored).  PUCCH estimation on the same objects:
+/* srs_cfg (a srsran_refsignal_srs_cfg_t*, void* as before for callers that pass NULL): recorded with cfg when it is
+ * valid for the cell; later srsran_chest_ul_estimate_srs calls then take the known sequence from the recorded
+ * configurations (chest_ul.c:633-634) and refuse a call whose M_sc differs from the recorded one (the reference reads
+ * past its pregenerated buffer there).  NULL: nothing recorded, as before.  PUCCH estimation on the same objects:
  * srsran_chest_ul_estimate_pucch in srsran_pucch.h */
 void srsran_chest_ul_pregen(srsran_chest_ul_t* q, srsran_refsignal_dmrs_pusch_cfg_t* cfg, void* srs_cfg);
 /* chest_ul.c:398-433.  cfg->use_cedron_alg with cfg->meas_ta_en is not provided (FFTW-based in the
@@ -110,6 +129,34 @@ int srsran_chest_ul_estimate_pusch(srsran_chest_ul_t*     q,
                                    srsran_pusch_cfg_t*    cfg,
                                    cf_t*                  input,
                                    srsran_chest_ul_res_t* res);
+/* chest_ul.c:612-647: the UE's SRS from the comb of the last symbol of `input` (host grid), chest_ul_estimate with one
+ * slot.  As the reference: cfo_hz = NAN; ta_us from srsran_vec_estimate_frequency with a pilot spacing of 1 (the
+ * comb's is 2, so ta_us is twice the delay); the M_sc smoothed (or copied) estimates go to res->ce contiguously at
+ * symbol SRSRAN_REFSIGNAL_UL_L(0, cp) from subcarrier 0 and nothing else of ce is touched.  A configuration that
+ * srsran_refsignal_srs_cfg_isvalid (srsran_ue_ul.h) refuses is SRSRAN_ERROR. */
+int srsran_chest_ul_estimate_srs(srsran_chest_ul_t*                 q,
+                                 srsran_ul_sf_cfg_t*                sf,
+                                 srsran_refsignal_srs_cfg_t*        cfg,
+                                 srsran_refsignal_dmrs_pusch_cfg_t* pusch_cfg,
+                                 cf_t*                              input,
+                                 srsran_chest_ul_res_t*             res);
+
+/* ---- added: the SRS of many UEs of one or more cells in one launch, asynchronous on `stream` ----
+ * Per entry: the cell's chest object, the device subframe grid, and a result object whose device side receives the
+ * estimate.  Nothing is enqueued when an entry is refused.  After the stream has drained,
+ * srsran_chest_ul_gpu_srs_result(res) fills the host fields and the ce row of one entry.  Results are bit-identical
+ * to srsran_chest_ul_estimate_srs on the same grids, in any order and composition; one result object per entry. */
+typedef struct {
+  srsran_chest_ul_t*                 q;
+  srsran_ul_sf_cfg_t*                sf;
+  srsran_refsignal_srs_cfg_t*        cfg;
+  srsran_refsignal_dmrs_pusch_cfg_t* pusch_cfg;
+  const cf_t*                        d_sf_symbols; /* device */
+  srsran_chest_ul_res_t*             res;
+} srsran_chest_ul_gpu_srs_t;
+
+int srsran_chest_ul_gpu_estimate_srs_batch(uint32_t nof_ue, const srsran_chest_ul_gpu_srs_t* ues, void* stream);
+int srsran_chest_ul_gpu_srs_result(srsran_chest_ul_res_t* res);
 
 typedef struct {
   uint8_t*           data;

@@ -13,6 +13,9 @@
  *   srsran_uci_data_t                        lib/include/srsran/phy/phch/uci_cfg.h:61-64
  *   srsran_refsignal_srs_pucch_shortened (as _cfg, without the unused object)
  *                                            lib/src/phy/ch_estimation/refsignal_ul.c:625-642
+ *   srsran_refsignal_srs_send_cs / _send_ue / _rb_start_cs / _rb_L_cs, and as _cell / _cfg (the cell in place of the
+ *   srsran_refsignal_ul_t object) srsran_refsignal_srs_M_sc, _pusch_shortened, _srs_gen, _srs_put, _srs_get
+ *                                            lib/src/phy/ch_estimation/refsignal_ul.c:560-622, 644-830, 870-924
  * with srsran_pusch_init_ue / srsran_pusch_encode / srsran_refsignal_dmrs_pusch_put_cell (srsran_pusch.h) and
  * srsran_ulsch_encode (srsran_sch.h) underneath.
  *
@@ -25,9 +28,16 @@
  * kernel (csrc/pucch_tx_kernel.hip), the same modulator, apply_cfo and apply_norm from (float)nof_prb / 15 / 10.
  * srsran_ue_ul_gpu_tx_batch (added) does the same for many UEs of one or more cells on device buffers.
  *
- * Not provided (SRSRAN_ERROR with a message): the SRS-only branch of srsran_ue_ul_encode, an SRS
- * configured for transmission in the subframe (srs_tx_enabled, ue_ul.c:453-462; every other subframe is encoded),
- * srsran_ue_ul_pregen_signals, srsran_ue_ul_set_cfr, a grant whose L_prb is not 2^a 3^b 5^c, filler bits.  srsran_ue_ul_dci_to_pusch_grant, srsran_ue_ul_pusch_hopping and the power
+ * A subframe that carries the UE's own sounding reference signal (srs_tx_enabled, ue_ul.c:453-462: ul_cfg.srs
+ * configured, a cell-specific and a UE-specific SRS subframe): with a grant or with PUCCH the SRS is added to the
+ * comb of the last symbol after the channel and its DMRS (add_srs, ue_ul.c:301-311, whatever sf->shortened says);
+ * without either, the SRS-only branch (srs_encode, ue_ul.c:435-451): the grid zeroed, the SRS, the same modulator,
+ * apply_cfo and apply_norm from (float)nof_prb / 15 / sqrtf(M_sc).  The sequence is formed on the GPU
+ * (csrc/srs_kernel.hip).  An SRS configuration that srsran_refsignal_srs_cfg_isvalid refuses is SRSRAN_ERROR in
+ * such a subframe.  For PUSCH sf->shortened is the caller's (srsran_refsignal_srs_pusch_shortened_cfg computes it).
+ *
+ * Not provided (SRSRAN_ERROR with a message): srsran_ue_ul_pregen_signals, srsran_ue_ul_set_cfr, a grant whose
+ * L_prb is not 2^a 3^b 5^c, filler bits.  srsran_ue_ul_dci_to_pusch_grant, srsran_ue_ul_pusch_hopping and the power
  * helpers are not declared: the caller supplies the grant with n_prb_tilde set, as for the receive side.
  */
 #ifndef SRSRAN_AMD_UE_UL_H
@@ -46,21 +56,7 @@ extern "C" {
 #define SRSRAN_SF_LEN(symbol_sz) ((symbol_sz) * 15)                                /* phy_common.h:134 */
 #define SRSRAN_SF_LEN_PRB(nof_prb) ((uint32_t)SRSRAN_SF_LEN(srsran_symbol_sz(nof_prb))) /* phy_common.h:138 */
 
-/* SRS configuration: data only (no SRS is generated) */
-typedef struct {
-  uint32_t subframe_config;
-  uint32_t bw_cfg;
-  bool     simul_ack;
-  uint32_t B;
-  uint32_t b_hop;
-  uint32_t n_srs;
-  uint32_t I_srs;
-  uint32_t k_tc;
-  uint32_t n_rrc;
-  bool     dedicated_enabled;
-  bool     common_enabled;
-  bool     configured;
-} srsran_refsignal_srs_cfg_t;
+/* srsran_refsignal_srs_cfg_t: srsran_pusch.h (the eNB's SRS estimator takes it too) */
 
 /* PUSCH hopping configuration: data only (the caller computes n_prb_tilde) */
 typedef struct {
@@ -129,7 +125,7 @@ int  srsran_ue_ul_set_cell(srsran_ue_ul_t* q, srsran_cell_t cell);
 int srsran_ue_ul_set_cfr(srsran_ue_ul_t* q, const void* cfr);
 int srsran_ue_ul_pregen_signals(srsran_ue_ul_t* q, srsran_ue_ul_cfg_t* cfg);
 
-/* ue_ul.c:618-659: 1 when a subframe was generated, 0 when there is nothing to send (out_buffer zeroed), -1 on
+/* ue_ul.c:618-659 (grant, then PUCCH, then SRS, then nothing): 1 when a subframe was generated, 0 when there is nothing to send (out_buffer zeroed), -1 on
  * error.  data->ptr: the host payload. */
 int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_cfg_t* cfg, srsran_pusch_data_t* data);
 
@@ -154,6 +150,46 @@ void srsran_refsignal_srs_pucch_shortened_cfg(srsran_ul_sf_cfg_t*         sf,
                                               srsran_refsignal_srs_cfg_t* srs_cfg,
                                               srsran_pucch_cfg_t*         pucch_cfg);
 
+/* ---- host helpers of the sounding reference signal, value-exact (refsignal_ul.c:560-622, 644-830, 870-924) ---- */
+/* added: what every entry point checks before it touches a grid: bw_cfg < 8, B < 4, b_hop < 4, k_tc < 2, n_srs < 8,
+ * n_rrc < 24, subframe_config < 15, I_srs < 637 and m_SRS,0 of the cell's bandwidth table <= nof_prb (the reference
+ * computes nof_prb / 2 - m_SRS,0 / 2 unsigned and writes outside its grid where that fails) */
+bool srsran_refsignal_srs_cfg_isvalid(const srsran_refsignal_srs_cfg_t* cfg, uint32_t nof_prb);
+/* 1: an SRS subframe, 0: not, SRSRAN_ERROR_INVALID_INPUTS out of range (FDD tables only, as the reference) */
+int srsran_refsignal_srs_send_cs(uint32_t subframe_config, uint32_t sf_idx);
+int srsran_refsignal_srs_send_ue(uint32_t I_srs, uint32_t tti);
+/* the cell-specific SRS region in PRB (the reference's unsigned arithmetic, also where m_SRS,0 > nof_prb) */
+uint32_t srsran_refsignal_srs_rb_start_cs(uint32_t bw_cfg, uint32_t nof_prb);
+uint32_t srsran_refsignal_srs_rb_L_cs(uint32_t bw_cfg, uint32_t nof_prb);
+/* M_sc,b = m_SRS,B 12 / 2, and k0 of the subframe with frequency hopping (the reference's static srs_k0_ue); 0 for a
+ * configuration that is not valid */
+uint32_t srsran_refsignal_srs_M_sc_cell(const srsran_cell_t* cell, const srsran_refsignal_srs_cfg_t* cfg);
+uint32_t srsran_refsignal_srs_k0_cell(const srsran_cell_t* cell, const srsran_refsignal_srs_cfg_t* cfg, uint32_t tti);
+/* writes sf->shortened: never for a RAR grant; in the UE's own SRS subframes unless the allocation is contiguous to
+ * the cell's SRS region; in the cell's SRS subframes where the allocation overlaps that region */
+void srsran_refsignal_srs_pusch_shortened_cfg(const srsran_cell_t*        cell,
+                                              srsran_ul_sf_cfg_t*         sf,
+                                              srsran_refsignal_srs_cfg_t* srs_cfg,
+                                              srsran_pusch_cfg_t*         pusch_cfg);
+/* r_srs: 2 M_sc values, the sequences of slots 2 sf_idx and 2 sf_idx + 1 (put / get use the first M_sc only, as the
+ * reference: with group or sequence hopping the SRS carries the sequence of slot 2 sf_idx).  sf_symbols: the
+ * subframe grid.  SRSRAN_ERROR_INVALID_INPUTS for a configuration that is not valid. */
+int srsran_refsignal_srs_gen_cell(const srsran_cell_t*               cell,
+                                  srsran_refsignal_srs_cfg_t*        cfg,
+                                  srsran_refsignal_dmrs_pusch_cfg_t* pusch_cfg,
+                                  uint32_t                           sf_idx,
+                                  cf_t*                              r_srs);
+int srsran_refsignal_srs_put_cell(const srsran_cell_t*        cell,
+                                  srsran_refsignal_srs_cfg_t* cfg,
+                                  uint32_t                    tti,
+                                  cf_t*                       r_srs,
+                                  cf_t*                       sf_symbols);
+int srsran_refsignal_srs_get_cell(const srsran_cell_t*        cell,
+                                  srsran_refsignal_srs_cfg_t* cfg,
+                                  uint32_t                    tti,
+                                  cf_t*                       r_srs,
+                                  cf_t*                       sf_symbols);
+
 /* ---- added: many UE subframes of one or more cells, asynchronous on `stream` ----
  * Every stage (TB CRC, code blocks, multiplexing + scrambling + mapping, transform precoding + DMRS, normalisation)
  * is one launch over all entries; the OFDM modulation is one launch pair per cell object, the CFO product one launch
@@ -165,6 +201,9 @@ void srsran_refsignal_srs_pucch_shortened_cfg(srsran_ul_sf_cfg_t*         sf,
  * An entry without grant_available is a PUCCH entry under srsran_ue_ul_encode's conditions (uci == NULL: an all-zero
  * value; d_data is ignored): all of them go through one PUCCH launch and share the modulator and normalisation
  * launches with the PUSCH entries; cfg->ul_cfg.pucch.format / n_pucch / pucch2_drs_bits and sf->shortened are written.
+ * An entry whose subframe carries the UE's SRS gets the SRS on its grid after its channel; all of them, and the
+ * entries with the SRS alone, go through one SRS launch after the PUSCH and PUCCH launches and share the modulator
+ * and normalisation launches.
  * An entry with nothing to send gets zeroed d_out / d_grid and is not an error. */
 typedef struct {
   srsran_ue_ul_t*           q;      /* the entry's cell (srsran_ue_ul_set_cell done) */
@@ -180,7 +219,7 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
 
 /* added, read-only: device pointers to the last encode on this object (the last batch entry naming it): the packed
  * scrambled bits (nof_bits / 8 bytes), the modulation symbols (nof_re) and the subframe grid (nof_grid REs); after a
- * PUCCH subframe the grid alone, with nof_bits = nof_re = 0.
+ * PUCCH or an SRS-only subframe the grid alone, with nof_bits = nof_re = 0.
  * Valid until the next encode on the object or on the object whose scratch served the batch; SRSRAN_ERROR before
  * the first. */
 int srsran_ue_ul_gpu_last(srsran_ue_ul_t* q,

@@ -1,6 +1,7 @@
 // srsran_4g_amd/csrc/pusch_api.cpp -- C-ABI of the PUSCH receive path (include/srsran_pusch.h) and, at the end, of
 // the UE's uplink transmit path (srsran_pusch_encode, include/srsran_ue_ul.h: the PUSCH branch and, over
-// pucch_tx_kernel.hip, the PUCCH branch of srsran_ue_ul_encode / srsran_ue_ul_gpu_tx_batch):
+// pucch_tx_kernel.hip and srs_kernel.hip, the PUCCH and SRS branches of srsran_ue_ul_encode /
+// srsran_ue_ul_gpu_tx_batch, with the host helpers of the sounding reference signal):
 // PUSCH DMRS generation (refsignal_ul.c:95-358 restated), the UL channel estimator object
 // (chest_ul.c:53-433) and srsran_pusch_t (pusch.c:108-471), over the kernels of pusch_kernel.hip,
 // llr_kernel.hip and the UL-SCH decoder of sch_api.cpp.
@@ -21,6 +22,7 @@
 #include "pusch_kernel.h"
 #include "pucch_tx_kernel.h"
 #include "pusch_tx_internal.h"
+#include "srs_kernel.h"
 #include "ulsch_batch.h"
 
 namespace srsran_amd {
@@ -112,8 +114,18 @@ uint32_t prime_below(uint32_t n)  // largest prime < n (srsran_prime_lower_than)
   return 2;
 }
 
+// the Zadoff-Chu root q of group u, base sequence v, in the float arithmetic of zc_sequence.c:214-227
+float zc_root(uint32_t u, uint32_t v, uint32_t Nzc)
+{
+  const float q_hat = (float)Nzc * (float)(u + 1) / 31.0f;
+  const float qf    = (((uint32_t)(2 * q_hat)) % 2 == 0) ? (float)(q_hat + 0.5 + v) : (float)(q_hat + 0.5 - v);
+  return (float)(uint32_t)qf;
+}
+
 // base sequence r_uv(n) e^{j alpha n} of 36.211 5.5.1, float arithmetic of zc_sequence.c:214-311
-void zc_sequence(uint32_t u, uint32_t v, float alpha, uint32_t nof_prb, cf_t* out)
+// fused: fl(arg + alpha i) with one rounding, as the reference's -mfma build evaluates it (the SRS, whose fixtures
+// record that build); otherwise alpha i is rounded first
+void zc_sequence(uint32_t u, uint32_t v, float alpha, uint32_t nof_prb, cf_t* out, bool fused = false)
 {
   const uint32_t     Mzc = nof_prb * SRSRAN_NRE;
   std::vector<float> arg(Mzc);
@@ -123,11 +135,9 @@ void zc_sequence(uint32_t u, uint32_t v, float alpha, uint32_t nof_prb, cf_t* ou
       arg[i] = (float)phi[i] * (float)M_PI_4;
     }
   } else {
-    const uint32_t Nzc   = prime_below(Mzc);
-    const float    n_sz  = (float)Nzc;
-    const float    q_hat = n_sz * (float)(u + 1) / 31.0f;
-    const float    qf    = (((uint32_t)(2 * q_hat)) % 2 == 0) ? (float)(q_hat + 0.5 + v) : (float)(q_hat + 0.5 - v);
-    const float    q     = (float)(uint32_t)qf;
+    const uint32_t Nzc  = prime_below(Mzc);
+    const float    n_sz = (float)Nzc;
+    const float    q    = zc_root(u, v, Nzc);
     for (uint32_t i = 0; i < Mzc; i++) {
       const float m = (float)(i % Nzc);
       arg[i]        = (float)(-M_PI * q * m * (m + 1) / n_sz);
@@ -135,7 +145,7 @@ void zc_sequence(uint32_t u, uint32_t v, float alpha, uint32_t nof_prb, cf_t* ou
   }
   for (uint32_t i = 0; i < Mzc; i++) {
     float s, c;
-    sincosf(arg[i] + alpha * (float)i, &s, &c);
+    sincosf(fused ? fmaf(alpha, (float)i, arg[i]) : arg[i] + alpha * (float)i, &s, &c);
     out[i] = cf_t{c, s};
   }
 }
@@ -174,6 +184,10 @@ bool dft_plan(uint32_t M, PuschUe& u)
   return n == 1;
 }
 
+// the sounding reference signal's host side, further down
+bool     srs_cfg_valid(const srsran_refsignal_srs_cfg_t& c, uint32_t nof_prb);
+uint32_t srs_M_sc(const srsran_refsignal_srs_cfg_t& c, uint32_t nof_prb);
+
 // ---------------- chest_ul device state ----------------
 struct ChestUlGpu {
   hipStream_t         stream = nullptr;
@@ -184,6 +198,11 @@ struct ChestUlGpu {
   std::vector<size_t> dmrs_off;  // (cs * 10 + sf) * 101 + n -> offset (values)
   DevBuf<float2>      d_grid;    // one subframe grid
   DevBuf<PuschUe>     d_desc;
+  // srsran_chest_ul_pregen with an SRS configuration: the known sequence comes from these (chest_ul.c:633-634)
+  bool                              srs_configured = false;
+  srsran_refsignal_srs_cfg_t        srs_cfg;
+  srsran_refsignal_dmrs_pusch_cfg_t srs_dmrs_cfg;
+  DevBuf<uint8_t>                   d_srs_desc;  // the SRS descriptors of a batch this object's scratch serves
 };
 
 struct ChestUlResGpu {
@@ -191,6 +210,10 @@ struct ChestUlResGpu {
   DevBuf<ChestUlOut> d_out;
   uint32_t    nof_re = 0;
   bool        valid  = false;   // d_ce holds the last estimate written to ce
+  // an SRS estimate enqueued on the device side and not yet fetched: where its ce row lies and how long it is
+  bool        srs_pending = false;
+  size_t      srs_off = 0;
+  uint32_t    srs_n = 0;
 };
 
 size_t dmrs_index(uint32_t cs, uint32_t sf, uint32_t n) { return ((size_t)cs * SRSRAN_NOF_SF_X_FRAME + sf) * 101 + n; }
@@ -495,11 +518,20 @@ int srsran_chest_ul_set_cell(srsran_chest_ul_t* q, srsran_cell_t cell)
 
 void srsran_chest_ul_pregen(srsran_chest_ul_t* q, srsran_refsignal_dmrs_pusch_cfg_t* cfg, void* srs_cfg)
 {
-  (void)srs_cfg;
   if (!q || !q->gpu || !cfg || !((ChestUlGpu*)q->gpu)->hop_ok) {
     return;
   }
   ChestUlGpu* g = (ChestUlGpu*)q->gpu;
+  if (srs_cfg) {  // chest_ul.c:200-203; the sequences themselves are formed by the estimator's kernel
+    const srsran_refsignal_srs_cfg_t& sc = *(const srsran_refsignal_srs_cfg_t*)srs_cfg;
+    if (srs_cfg_valid(sc, q->cell.nof_prb) && cfg->delta_ss < SRSRAN_NOF_DELTA_SS) {
+      g->srs_cfg        = sc;
+      g->srs_dmrs_cfg   = *cfg;
+      g->srs_configured = true;
+    } else {
+      fprintf(stderr, "[srsran_chest_ul] Invalid SRS configuration: not recorded\n");
+    }
+  }
   // every (n_dmrs, subframe, valid L_prb <= cell PRB) sequence, as srsran_refsignal_dmrs_pusch_pregen
   const uint32_t nmax = std::min(q->cell.nof_prb, g->max_prb ? g->max_prb : q->cell.nof_prb);
   g->dmrs_off.assign(dmrs_index(SRSRAN_NOF_CSHIFT, 0, 0), (size_t)-1);
@@ -1102,6 +1134,7 @@ struct UeUlGpu {
   uint32_t  cfo_len = 0;
   DevBuf<uint8_t> d_io;    // sync API: payload, then the output samples
   DevBuf<uint8_t> d_ptx;   // the PUCCH descriptors of a batch this object's scratch serves
+  DevBuf<uint8_t> d_stx;   // its SRS descriptors
   // srsran_ue_ul_gpu_last
   const uint8_t* last_s = nullptr;
   const float2*  last_d = nullptr;
@@ -1112,8 +1145,7 @@ struct UeUlGpu {
 
 // srs_tx_enabled (ue_ul.c:453-462): the subframe carries this UE's SRS when it is a cell-specific SRS subframe
 // (srsran_refsignal_srs_send_cs, refsignal_ul.c:703-749, 36.211 Table 5.5.3.3-1) and a UE-specific one
-// (srsran_refsignal_srs_send_ue, refsignal_ul.c:560-622, 36.213 Table 8.2-1).  SRS is not generated: such a subframe
-// is refused, every other one is encoded as the reference encodes it.
+// (srsran_refsignal_srs_send_ue, refsignal_ul.c:560-622, 36.213 Table 8.2-1).
 bool srs_send_cs(uint32_t subframe_config, uint32_t sf_idx)
 {
   static const uint32_t T_sfc[15] = {1, 2, 2, 5, 5, 5, 5, 5, 5, 10, 10, 10, 10, 10, 10};
@@ -1146,17 +1178,137 @@ bool srs_send_ue(uint32_t I_srs, uint32_t tti)
   while (I_srs >= first[k + 1]) {
     k++;
   }
-  return (tti - (I_srs - first[k])) % T_srs[k] == 0;  // unsigned, as the reference's (tti - Toffset) % T_srs
+  return (tti - (I_srs - first[k])) % T_srs[k] == 0;  // unsigned, as the reference's (tti - Toffset) % T_srs; tti >= 10240 above: the
+                                                      // reference's helper answers an error there, which srs_tx_enabled does not take for 1
 }
 
-bool srs_in_subframe(const srsran_ue_ul_cfg_t* cfg, uint32_t tti)
+bool srs_tx_enabled(const srsran_refsignal_srs_cfg_t& srs, uint32_t tti)
 {
-  const srsran_refsignal_srs_cfg_t& srs = cfg->ul_cfg.srs;
-  if (srs.configured && srs_send_cs(srs.subframe_config, tti % 10) && srs_send_ue(srs.I_srs, tti)) {
-    fprintf(stderr, "[srsran_ue_ul] SRS transmission is not provided (tti %u carries this UE's SRS)\n", tti);
-    return true;
+  return srs.configured && srs_send_cs(srs.subframe_config, tti % 10) && srs_send_ue(srs.I_srs, tti);
+}
+
+// 36.211 Tables 5.5.3.2-1 .. -4 as refsignal_ul.c:65-92 holds them: m_SRS,b and N_b by [bandwidth table][b][C_SRS]
+constexpr uint32_t kMsrs[4][4][8] = {
+    {{36, 32, 24, 20, 16, 12, 8, 4}, {12, 16, 4, 4, 4, 4, 4, 4}, {4, 8, 4, 4, 4, 4, 4, 4}, {4, 4, 4, 4, 4, 4, 4, 4}},
+    {{48, 48, 40, 36, 32, 24, 20, 16}, {24, 16, 20, 12, 16, 4, 4, 4}, {12, 8, 4, 4, 8, 4, 4, 4}, {4, 4, 4, 4, 4, 4, 4, 4}},
+    {{72, 64, 60, 48, 48, 40, 36, 32}, {24, 32, 20, 24, 16, 20, 12, 16}, {12, 16, 4, 12, 8, 4, 4, 8}, {4, 4, 4, 4, 4, 4, 4, 4}},
+    {{96, 96, 80, 72, 64, 60, 48, 48}, {48, 32, 40, 24, 32, 20, 24, 16}, {24, 16, 20, 12, 16, 4, 12, 8}, {4, 4, 4, 4, 4, 4, 4, 4}}};
+constexpr uint32_t kNb[4][4][8] = {
+    {{1, 1, 1, 1, 1, 1, 1, 1}, {3, 2, 6, 5, 4, 3, 2, 1}, {3, 2, 1, 1, 1, 1, 1, 1}, {1, 2, 1, 1, 1, 1, 1, 1}},
+    {{1, 1, 1, 1, 1, 1, 1, 1}, {2, 3, 2, 3, 2, 6, 5, 4}, {2, 2, 5, 3, 2, 1, 1, 1}, {3, 2, 1, 1, 2, 1, 1, 1}},
+    {{1, 1, 1, 1, 1, 1, 1, 1}, {3, 2, 3, 2, 3, 2, 3, 2}, {2, 2, 5, 2, 2, 5, 3, 2}, {3, 4, 1, 3, 2, 1, 1, 2}},
+    {{1, 1, 1, 1, 1, 1, 1, 1}, {2, 3, 2, 3, 2, 3, 2, 3}, {2, 2, 2, 2, 2, 5, 2, 2}, {6, 4, 5, 3, 4, 1, 3, 2}}};
+
+// refsignal_ul.c:751-762: the table by the cell's bandwidth
+uint32_t srs_bw_table(uint32_t nof_prb) { return nof_prb <= 40 ? 0 : nof_prb <= 60 ? 1 : nof_prb <= 80 ? 2 : 3; }
+
+uint32_t srs_T(uint32_t I_srs)  // 36.213 Table 8.2-1 (refsignal_ul.c:560-584), 0 from 637 on
+{
+  static const uint32_t first[9] = {0, 2, 7, 17, 37, 77, 157, 317, 637}, T_srs[8] = {2, 5, 10, 20, 40, 80, 160, 320};
+  for (uint32_t k = 0; k < 8; k++) {
+    if (I_srs < first[k + 1]) {
+      return T_srs[k];
+    }
   }
-  return false;
+  return 0;
+}
+
+bool srs_cfg_valid(const srsran_refsignal_srs_cfg_t& c, uint32_t nof_prb)
+{
+  return c.bw_cfg < 8 && c.B < 4 && c.b_hop < 4 && c.k_tc < 2 && c.n_srs < 8 && c.n_rrc < 24 && c.subframe_config < 15 &&
+         c.I_srs < 637 && kMsrs[srs_bw_table(nof_prb)][0][c.bw_cfg] <= nof_prb;
+}
+
+uint32_t srs_M_sc(const srsran_refsignal_srs_cfg_t& c, uint32_t nof_prb)
+{
+  return kMsrs[srs_bw_table(nof_prb)][c.B][c.bw_cfg] * SRSRAN_NRE / 2;
+}
+
+// srs_Fb (refsignal_ul.c:782-802).  The odd branch keeps the reference's form: floor(N_b / 2) (n_SRS / prod), without
+// the outer floor of 36.211 5.5.3.2 (n_SRS / prod is an integer quotient already).
+uint32_t srs_Fb(const srsran_refsignal_srs_cfg_t& c, uint32_t b, uint32_t nof_prb, uint32_t tti)
+{
+  const uint32_t T = srs_T(c.I_srs), t = srs_bw_table(nof_prb);
+  if (!T) {
+    return 0;
+  }
+  const uint32_t n_srs = tti / T, N_b = kNb[t][b][c.bw_cfg];
+  uint32_t       prod_1 = 1;
+  for (uint32_t bp = c.b_hop + 1; bp < b; bp++) {
+    prod_1 *= kNb[t][bp][c.bw_cfg];
+  }
+  const uint32_t prod_2 = prod_1 * N_b;
+  if (N_b % 2 == 0) {
+    return (N_b / 2) * ((n_srs % prod_2) / prod_1) + ((n_srs % prod_2) / prod_1 / 2);
+  }
+  return (N_b / 2) * (n_srs / prod_1);
+}
+
+// srs_k0_ue (refsignal_ul.c:805-825) of a valid configuration
+uint32_t srs_k0(const srsran_refsignal_srs_cfg_t& c, uint32_t nof_prb, uint32_t tti)
+{
+  const uint32_t t  = srs_bw_table(nof_prb);
+  uint32_t       k0 = (nof_prb / 2 - kMsrs[t][0][c.bw_cfg] / 2) * SRSRAN_NRE + c.k_tc;
+  for (uint32_t b = 0; b <= c.B; b++) {
+    const uint32_t m_srs = kMsrs[t][b][c.bw_cfg], m_sc = m_srs * SRSRAN_NRE / 2;
+    uint32_t       nb    = 4 * c.n_rrc / m_srs;
+    if (b > c.b_hop) {
+      nb += srs_Fb(c, b, nof_prb, tti);
+    }
+    k0 += 2 * m_sc * (nb % kNb[t][b][c.bw_cfg]);
+  }
+  return k0;
+}
+
+// What compute_r (refsignal_ul.c:229-252) hands to srsran_zc_sequence_generate_lte for the SRS of slot ns
+// (refsignal_ul.c:882-883): nof_prb = M_sc / 12, delta_ss = 0 in u, the DMRS configuration's delta_ss in the row of v.
+void srs_uv(const srsran_cell_t& cell, const UlHopping& h, const srsran_refsignal_dmrs_pusch_cfg_t& d, uint32_t M_sc,
+            uint32_t ns, uint32_t* u, uint32_t* v)
+{
+  *u = ((d.group_hopping_en ? h.f_gh[ns] : 0) + (cell.id % 30)) % 30;
+  *v = (M_sc / SRSRAN_NRE >= 6 && d.sequence_hopping_en) ? h.v[ns][d.delta_ss] : 0;
+}
+
+float srs_alpha(uint32_t n_srs) { return (float)(2 * M_PI * n_srs / 8); }
+
+// The sequence of subframe sf_idx for the kernels: that of slot 2 sf_idx
+SrsSeq srs_seq(const srsran_cell_t& cell, const UlHopping& h, uint32_t n_srs, const srsran_refsignal_dmrs_pusch_cfg_t& d,
+               uint32_t m_sc, uint32_t sf_idx)
+{
+  SrsSeq q;
+  memset(&q, 0, sizeof(q));
+  uint32_t u, v;
+  srs_uv(cell, h, d, m_sc, 2 * sf_idx, &u, &v);
+  q.alpha = srs_alpha(n_srs);
+  if (m_sc == 24) {
+    memcpy(q.phi, kZcPhi24[u], 24);
+  } else {
+    q.n_zc = prime_below(m_sc);
+    q.q    = zc_root(u, v, q.n_zc);
+  }
+  return q;
+}
+
+// The descriptor of the UE's SRS in subframe tti: the sequence of slot 2 (tti % 10) (srsran_refsignal_srs_put maps the
+// first of the two sequences srsran_refsignal_srs_gen writes, also in the last symbol of slot 1).  grid is left null.
+int srs_tx_prepare(const srsran_cell_t& cell, const UlHopping& h, const srsran_refsignal_srs_cfg_t& c,
+                   const srsran_refsignal_dmrs_pusch_cfg_t& d, uint32_t tti, SrsTxUe* out)
+{
+  if (!srs_cfg_valid(c, cell.nof_prb) || d.delta_ss >= SRSRAN_NOF_DELTA_SS) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  SrsTxUe s;
+  memset(&s, 0, sizeof(s));
+  s.ncell_re = cell.nof_prb * SRSRAN_NRE;
+  s.nsym     = 2 * nsymb_slot(cell.cp);
+  s.m_sc     = srs_M_sc(c, cell.nof_prb);
+  s.k0       = srs_k0(c, cell.nof_prb, tti);
+  if (s.m_sc == 0 || s.k0 + 2 * (s.m_sc - 1) >= s.ncell_re) {  // the comb stays inside the last symbol's row
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  s.seq = srs_seq(cell, h, c.n_srs, d, s.m_sc, tti % SRSRAN_NOF_SF_X_FRAME);
+  *out  = s;
+  return SRSRAN_SUCCESS;
 }
 
 }  // namespace
@@ -1368,6 +1520,279 @@ void srsran_refsignal_srs_pucch_shortened_cfg(srsran_ul_sf_cfg_t*         sf,
                   srs_send_cs(srs_cfg->subframe_config, sf->tti % 10);
 }
 
+// ---------------- sounding reference signal, host side (refsignal_ul.c:560-622, 644-830, 870-924) ----------------
+bool srsran_refsignal_srs_cfg_isvalid(const srsran_refsignal_srs_cfg_t* cfg, uint32_t nof_prb)
+{
+  return cfg && nof_prb >= 6 && nof_prb <= SRSRAN_MAX_PRB && srs_cfg_valid(*cfg, nof_prb);
+}
+
+int srsran_refsignal_srs_send_cs(uint32_t subframe_config, uint32_t sf_idx)
+{
+  if (subframe_config >= 15 || sf_idx >= 10) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return srs_send_cs(subframe_config, sf_idx) ? 1 : 0;
+}
+
+int srsran_refsignal_srs_send_ue(uint32_t I_srs, uint32_t tti)
+{
+  if (I_srs >= 1024 || tti >= 10240) {  // refsignal_ul.c:592: from 637 to 1023 the answer is 0, not an error
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return srs_send_ue(I_srs, tti) ? 1 : 0;
+}
+
+// refsignal_ul.c:765-780; unsigned as there: it wraps where m_SRS,0 > nof_prb, which srs_cfg_isvalid refuses
+uint32_t srsran_refsignal_srs_rb_start_cs(uint32_t bw_cfg, uint32_t nof_prb)
+{
+  return bw_cfg < 8 ? nof_prb / 2 - kMsrs[srs_bw_table(nof_prb)][0][bw_cfg] / 2 : 0;
+}
+
+uint32_t srsran_refsignal_srs_rb_L_cs(uint32_t bw_cfg, uint32_t nof_prb)
+{
+  return bw_cfg < 8 ? kMsrs[srs_bw_table(nof_prb)][0][bw_cfg] : 0;
+}
+
+uint32_t srsran_refsignal_srs_M_sc_cell(const srsran_cell_t* cell, const srsran_refsignal_srs_cfg_t* cfg)
+{
+  return cell && srsran_refsignal_srs_cfg_isvalid(cfg, cell->nof_prb) ? srs_M_sc(*cfg, cell->nof_prb) : 0;
+}
+
+uint32_t srsran_refsignal_srs_k0_cell(const srsran_cell_t* cell, const srsran_refsignal_srs_cfg_t* cfg, uint32_t tti)
+{
+  return cell && srsran_refsignal_srs_cfg_isvalid(cfg, cell->nof_prb) ? srs_k0(*cfg, cell->nof_prb, tti) : 0;
+}
+
+// refsignal_ul.c:644-697
+void srsran_refsignal_srs_pusch_shortened_cfg(const srsran_cell_t*        cell,
+                                              srsran_ul_sf_cfg_t*         sf,
+                                              srsran_refsignal_srs_cfg_t* srs_cfg,
+                                              srsran_pusch_cfg_t*         pusch_cfg)
+{
+  bool shortened = false;
+  if (pusch_cfg->grant.is_rar) {  // no SRS with a RAR grant or its retransmissions
+    sf->shortened = false;
+    return;
+  }
+  if (srs_cfg->configured) {
+    const uint32_t k0_srs = srsran_refsignal_srs_rb_start_cs(srs_cfg->bw_cfg, cell->nof_prb);
+    const uint32_t nrb    = srsran_refsignal_srs_rb_L_cs(srs_cfg->bw_cfg, cell->nof_prb);
+    const uint32_t L      = pusch_cfg->grant.L_prb;
+    const bool     cs     = srs_send_cs(srs_cfg->subframe_config, sf->tti % 10);
+    if (cs && srs_send_ue(srs_cfg->I_srs, sf->tti)) {
+      // the UE's own SRS subframe: shortened, overlapping or not, unless the allocation is contiguous to the region
+      shortened = true;
+      for (uint32_t ns = 0; ns < 2 && shortened; ns++) {
+        const uint32_t n = pusch_cfg->grant.n_prb_tilde[ns];
+        if (n == k0_srs + nrb || n + L == k0_srs) {
+          shortened = false;
+        }
+      }
+    }
+    if (!shortened && cs) {  // a cell SRS subframe: shortened where the allocation meets the cell's SRS region
+      for (uint32_t ns = 0; ns < 2 && !shortened; ns++) {
+        const uint32_t n = pusch_cfg->grant.n_prb_tilde[ns];
+        if ((n >= k0_srs && n < k0_srs + nrb) || (n + L > k0_srs && n + L < k0_srs + nrb) ||
+            (n <= k0_srs && n + L >= k0_srs + nrb)) {
+          shortened = true;
+        }
+      }
+    }
+  }
+  sf->shortened = shortened;
+}
+
+// refsignal_ul.c:870-888: the sequences of both slots of the subframe, M_sc values each
+int srsran_refsignal_srs_gen_cell(const srsran_cell_t*               cell,
+                                  srsran_refsignal_srs_cfg_t*        cfg,
+                                  srsran_refsignal_dmrs_pusch_cfg_t* pusch_cfg,
+                                  uint32_t                           sf_idx,
+                                  cf_t*                              r_srs)
+{
+  if (!cell || !cfg || !pusch_cfg || !r_srs || !cell_valid(*cell) || sf_idx >= SRSRAN_NOF_SF_X_FRAME ||
+      !srs_cfg_valid(*cfg, cell->nof_prb) || pusch_cfg->delta_ss >= SRSRAN_NOF_DELTA_SS) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  UlHopping h;
+  hopping_tables(*cell, h);
+  const uint32_t M_sc = srs_M_sc(*cfg, cell->nof_prb);
+  for (uint32_t ns = 2 * sf_idx; ns < 2 * (sf_idx + 1); ns++) {
+    uint32_t u, v;
+    srs_uv(*cell, h, *pusch_cfg, M_sc, ns, &u, &v);
+    zc_sequence(u, v, srs_alpha(cfg->n_srs), M_sc / SRSRAN_NRE, r_srs + (ns % 2) * M_sc, true);
+  }
+  return SRSRAN_SUCCESS;
+}
+
+namespace {
+// refsignal_ul.c:890-924: the comb of the last symbol, from or to the first M_sc values of r_srs
+int srs_put_get(const srsran_cell_t* cell, srsran_refsignal_srs_cfg_t* cfg, uint32_t tti, cf_t* r_srs, cf_t* sf_symbols,
+                bool put)
+{
+  if (!cell || !cfg || !r_srs || !sf_symbols || !cell_valid(*cell) || !srs_cfg_valid(*cfg, cell->nof_prb)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  const uint32_t M_sc = srs_M_sc(*cfg, cell->nof_prb), k0 = srs_k0(*cfg, cell->nof_prb, tti);
+  const uint32_t ncell = cell->nof_prb * SRSRAN_NRE;
+  if (k0 + 2 * (M_sc - 1) >= ncell) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  cf_t* row = sf_symbols + (size_t)(2 * nsymb_slot(cell->cp) - 1) * ncell + k0;
+  for (uint32_t i = 0; i < M_sc; i++) {
+    if (put) {
+      row[2 * i] = r_srs[i];
+    } else {
+      r_srs[i] = row[2 * i];
+    }
+  }
+  return SRSRAN_SUCCESS;
+}
+}  // namespace
+
+int srsran_refsignal_srs_put_cell(const srsran_cell_t* cell, srsran_refsignal_srs_cfg_t* cfg, uint32_t tti, cf_t* r_srs,
+                                  cf_t* sf_symbols)
+{
+  return srs_put_get(cell, cfg, tti, r_srs, sf_symbols, true);
+}
+
+int srsran_refsignal_srs_get_cell(const srsran_cell_t* cell, srsran_refsignal_srs_cfg_t* cfg, uint32_t tti, cf_t* r_srs,
+                                  cf_t* sf_symbols)
+{
+  return srs_put_get(cell, cfg, tti, r_srs, sf_symbols, false);
+}
+
+// ---------------- chest_ul.c:612-647 ----------------
+int srsran_chest_ul_gpu_estimate_srs_batch(uint32_t nof_ue, const srsran_chest_ul_gpu_srs_t* ues, void* stream)
+{
+  if (nof_ue == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (!ues) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  hipStream_t          st = (hipStream_t)stream;
+  std::vector<SrsRxUe> desc(nof_ue);
+  for (uint32_t i = 0; i < nof_ue; i++) {
+    const srsran_chest_ul_gpu_srs_t& e = ues[i];
+    if (!e.q || !e.q->gpu || !e.sf || !e.cfg || !e.pusch_cfg || !e.d_sf_symbols || !e.res || !e.res->gpu ||
+        !((ChestUlGpu*)e.q->gpu)->hop_ok) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    for (uint32_t k = 0; k < i; k++) {
+      if (ues[k].res == e.res) {
+        return SRSRAN_ERROR_INVALID_INPUTS;
+      }
+    }
+    const srsran_chest_ul_t* q  = e.q;
+    ChestUlGpu*              g  = (ChestUlGpu*)q->gpu;
+    ChestUlResGpu*           rg = (ChestUlResGpu*)e.res->gpu;
+    const srsran_cell_t&     cell = q->cell;
+    if (!srs_cfg_valid(*e.cfg, cell.nof_prb) || e.pusch_cfg->delta_ss >= SRSRAN_NOF_DELTA_SS) {
+      fprintf(stderr, "[srsran_chest_ul] Invalid SRS configuration\n");
+      return SRSRAN_ERROR;
+    }
+    const uint32_t ncell = cell.nof_prb * SRSRAN_NRE, nsym = 2 * nsymb_slot(cell.cp);
+    const uint32_t M_sc = srs_M_sc(*e.cfg, cell.nof_prb), k0 = srs_k0(*e.cfg, cell.nof_prb, e.sf->tti);
+    const size_t   off  = (size_t)SRSRAN_REFSIGNAL_UL_L(0, cell.cp) * ncell;
+    if (M_sc > SRS_MAX_M_SC || k0 + 2 * (M_sc - 1) >= ncell || off + M_sc > rg->nof_re || (size_t)ncell * nsym > rg->nof_re) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    // the known pilots: generated from the call's configurations, or those srsran_chest_ul_pregen recorded
+    const srsran_refsignal_srs_cfg_t&        kc = g->srs_configured ? g->srs_cfg : *e.cfg;
+    const srsran_refsignal_dmrs_pusch_cfg_t& kd = g->srs_configured ? g->srs_dmrs_cfg : *e.pusch_cfg;
+    if (g->srs_configured && srs_M_sc(kc, cell.nof_prb) != M_sc) {
+      fprintf(stderr, "[srsran_chest_ul] SRS of %u subcarriers against pregenerated sequences of %u\n", M_sc,
+              srs_M_sc(kc, cell.nof_prb));
+      return SRSRAN_ERROR;
+    }
+    SrsRxUe& u = desc[i];
+    memset(&u, 0, sizeof(u));
+    u.grid     = (const float2*)e.d_sf_symbols;
+    u.ce       = rg->d_ce + off;
+    u.out      = rg->d_out;
+    u.ncell_re = ncell;
+    u.nsym     = nsym;
+    u.k0       = k0;
+    u.m_sc     = M_sc;
+    u.smooth   = q->smooth_filter_len == 3;
+    for (int k = 0; k < 3; k++) {
+      u.filt[k] = u.smooth ? q->smooth_filter[k] : 0.f;
+    }
+    const float w = q->smooth_filter[0];  // estimate_noise_pilots' calibration (chest_ul.c:220-225)
+    u.noise_div   = (double)(float)(7.419 * w * w + 0.1117 * w - 0.005387) * 0.8;
+    u.seq         = srs_seq(cell, g->hop, kc.n_srs, kd, M_sc, e.sf->tti % SRSRAN_NOF_SF_X_FRAME);
+  }
+  ChestUlGpu* g0 = (ChestUlGpu*)ues[0].q->gpu;
+  if (!g0->d_srs_desc.reserve(desc.size() * sizeof(SrsRxUe))) {
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t i = 0; i < nof_ue; i++) {  // the device estimate in line with the host's where the host's is newer
+    ChestUlResGpu* rg = (ChestUlResGpu*)ues[i].res->gpu;
+    if (!rg->valid && hipMemcpyAsync(rg->d_ce, ues[i].res->ce, (size_t)rg->nof_re * sizeof(float2), hipMemcpyHostToDevice,
+                                     st) != hipSuccess) {
+      return SRSRAN_ERROR;
+    }
+  }
+  if (hipMemcpyAsync(g0->d_srs_desc, desc.data(), desc.size() * sizeof(SrsRxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
+      srs_chest_launch((const SrsRxUe*)g0->d_srs_desc.get(), nof_ue, st) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t i = 0; i < nof_ue; i++) {
+    ChestUlResGpu* rg = (ChestUlResGpu*)ues[i].res->gpu;
+    rg->srs_pending   = true;
+    rg->srs_off       = (size_t)(desc[i].ce - rg->d_ce.get());
+    rg->srs_n         = desc[i].m_sc;
+    rg->valid         = true;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_chest_ul_gpu_srs_result(srsran_chest_ul_res_t* res)
+{
+  if (!res || !res->gpu || !res->ce) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  ChestUlResGpu* rg = (ChestUlResGpu*)res->gpu;
+  if (!rg->srs_pending) {
+    return SRSRAN_ERROR;
+  }
+  ChestUlOut o;
+  if (hipMemcpy(&o, rg->d_out, sizeof(o), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(res->ce + rg->srs_off, rg->d_ce + rg->srs_off, rg->srs_n * sizeof(float2), hipMemcpyDeviceToHost) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  rg->srs_pending = false;
+  finish_chest_res(res, o);
+  return SRSRAN_SUCCESS;
+}
+
+int srsran_chest_ul_estimate_srs(srsran_chest_ul_t*                 q,
+                                 srsran_ul_sf_cfg_t*                sf,
+                                 srsran_refsignal_srs_cfg_t*        cfg,
+                                 srsran_refsignal_dmrs_pusch_cfg_t* pusch_cfg,
+                                 cf_t*                              input,
+                                 srsran_chest_ul_res_t*             res)
+{
+  if (!q || !q->gpu || !sf || !cfg || !pusch_cfg || !input || !res || !res->gpu) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  ChestUlGpu*  g     = (ChestUlGpu*)q->gpu;
+  const size_t sf_re = (size_t)q->cell.nof_prb * SRSRAN_NRE * 2 * nsymb_slot(q->cell.cp);
+  if (sf_re == 0 || !g->d_grid.reserve(sf_re) ||
+      hipMemcpyAsync(g->d_grid, input, sf_re * sizeof(float2), hipMemcpyHostToDevice, g->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  srsran_chest_ul_gpu_srs_t e = {q, sf, cfg, pusch_cfg, (const cf_t*)g->d_grid.get(), res};
+  int                       ret = srsran_chest_ul_gpu_estimate_srs_batch(1, &e, g->stream);
+  if (hipStreamSynchronize(g->stream) != hipSuccess) {
+    ret = SRSRAN_ERROR;
+  }
+  if (ret != SRSRAN_SUCCESS) {
+    return ret == SRSRAN_ERROR_INVALID_INPUTS ? ret : SRSRAN_ERROR;
+  }
+  return srsran_chest_ul_gpu_srs_result(res);
+}
+
 int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* entries, void* stream)
 {
   if (nof_ue == 0) {
@@ -1376,25 +1801,32 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
   if (!entries) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  enum { K_PUSCH, K_PUCCH, K_NONE };
+  enum { K_PUSCH, K_PUCCH, K_SRS, K_NONE };  // the branch order of ue_ul.c:640-656
   hipStream_t                  st = (hipStream_t)stream;
   std::vector<srsran_ue_ul_t*> objs;            // the distinct cell objects, in order of first use
   std::vector<uint32_t>        slot(nof_ue);    // the entry's index among its object's transmissions
   std::vector<uint32_t>        count, samples;  // per object: transmissions, transmissions that want samples
   std::vector<uint32_t>        obj_of(nof_ue), kind(nof_ue), idx(nof_ue);  // idx: among the entries of its kind
   std::vector<PucchTxUe>       pdesc;
-  uint32_t                     npusch = 0;
+  std::vector<SrsTxUe>         sdesc;           // the SRS of every entry whose subframe carries it, with or without a channel
+  std::vector<int>             srs_of(nof_ue, -1);
+  uint32_t                     npusch = 0, nsrs_only = 0;
   for (uint32_t i = 0; i < nof_ue; i++) {
     const srsran_ue_ul_gpu_entry_t& e = entries[i];
     if (!e.q || !e.q->gpu || !e.sf || !e.cfg || !((UeUlGpu*)e.q->gpu)->hop_ok) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
+    // add_srs (ue_ul.c:301-311) or srs_encode (435-451); checked before anything of the caller's is written
+    const bool with_srs = srs_tx_enabled(e.cfg->ul_cfg.srs, e.sf->tti);
+    SrsTxUe    srs_d;
+    if (with_srs && srs_tx_prepare(e.q->cell, ((UeUlGpu*)e.q->gpu)->hop, e.cfg->ul_cfg.srs, e.cfg->ul_cfg.dmrs, e.sf->tti,
+                                   &srs_d) != SRSRAN_SUCCESS) {
+      fprintf(stderr, "[srsran_ue_ul] Invalid SRS configuration (tti %u carries this UE's SRS)\n", e.sf->tti);
+      return SRSRAN_ERROR;
+    }
     if (e.cfg->grant_available) {
       kind[i] = K_PUSCH;
       idx[i]  = npusch++;
-      if (srs_in_subframe(e.cfg, e.sf->tti)) {
-        return SRSRAN_ERROR;
-      }
     } else {
       // the PUCCH branch of ue_ul.c:642-648 and pucch_encode (510-541) up to the kernel
       srsran_pucch_cfg_t*     pc = &e.cfg->ul_cfg.pucch;
@@ -1417,9 +1849,6 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
           return SRSRAN_ERROR;
         }
       }
-      if (srs_in_subframe(e.cfg, e.sf->tti)) {  // with PUCCH or alone
-        return SRSRAN_ERROR;
-      }
       if (kind[i] == K_PUCCH) {
         srsran_uci_value_t value2 = value;  // the value that is encoded: b(0) b(1) of the selection go here
         srsran_ue_ul_pucch_resource_selection(&e.q->cell, pc, &pc->uci_cfg, &value, value2.ack.ack_value);
@@ -1435,6 +1864,14 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
         idx[i] = (uint32_t)pdesc.size();
         pdesc.push_back(d);
       }
+    }
+    if (with_srs) {
+      if (kind[i] == K_NONE) {
+        kind[i] = K_SRS;
+        idx[i]  = nsrs_only++;
+      }
+      srs_of[i] = (int)sdesc.size();
+      sdesc.push_back(srs_d);
     }
     size_t o = std::find(objs.begin(), objs.end(), e.q) - objs.begin();
     if (o == objs.size()) {
@@ -1458,7 +1895,8 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
     }
   }
   std::vector<TxReq>     r(npusch);
-  std::vector<PuschTxUe> pnorm(pdesc.size(), PuschTxUe{});  // the normalisation stage of the PUCCH entries
+  // the normalisation stage of the PUCCH entries, then of the SRS-only entries
+  std::vector<PuschTxUe> pnorm(pdesc.size() + nsrs_only, PuschTxUe{});
   for (uint32_t i = 0; i < nof_ue; i++) {
     const srsran_ue_ul_gpu_entry_t& e = entries[i];
     srsran_ue_ul_t*                 q = e.q;
@@ -1474,17 +1912,27 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
     const float2* samples_in = g->d_samp + (size_t)slot[i] * q->fft.sf_sz;
     const uint32_t norm_mode = e.cfg->normalize_mode == SRSRAN_UE_UL_NORMALIZE_MODE_FORCE_AMPLITUDE ? 1 : 0;
     const float   force_peak = e.cfg->force_peak_amplitude > 0 ? e.cfg->force_peak_amplitude : 1.0f;
-    if (kind[i] == K_PUCCH) {
-      PucchTxUe& d = pdesc[idx[i]];
-      d.grid       = g->d_grid + slot[i] * sf_re;
-      d.zero_rest  = 1;
+    if (srs_of[i] >= 0) {
+      SrsTxUe& d  = sdesc[srs_of[i]];
+      d.grid      = g->d_grid + slot[i] * sf_re;
+      d.zero_rest = kind[i] == K_SRS ? 1 : 0;
+    }
+    if (kind[i] == K_PUCCH || kind[i] == K_SRS) {
+      const bool pucch = kind[i] == K_PUCCH;
+      if (pucch) {
+        PucchTxUe& d = pdesc[idx[i]];
+        d.grid       = g->d_grid + slot[i] * sf_re;
+        d.zero_rest  = 1;
+      }
       if (e.d_out) {
-        PuschTxUe& u  = pnorm[idx[i]];
+        PuschTxUe& u  = pnorm[pucch ? idx[i] : pdesc.size() + idx[i]];
         u.samples_in  = samples_in;
         u.samples_out = (float2*)e.d_out;
         u.sf_len      = q->fft.sf_sz;
         u.norm_mode   = norm_mode;
-        u.norm_factor = (float)q->cell.nof_prb / 15 / 10;  // ue_ul.c:548: a float quotient here
+        // ue_ul.c:548 / 446: a float quotient here
+        u.norm_factor = pucch ? (float)q->cell.nof_prb / 15 / 10
+                              : (float)q->cell.nof_prb / 15 / sqrtf((float)sdesc[srs_of[i]].m_sc);
         u.force_peak  = force_peak;
       }
       continue;
@@ -1510,7 +1958,7 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
       t.force_peak  = force_peak;
     }
   }
-  if (npusch == 0 && pdesc.empty()) {
+  if (npusch == 0 && pdesc.empty() && sdesc.empty()) {
     return SRSRAN_SUCCESS;
   }
   std::vector<PuschTxUe> desc;
@@ -1524,6 +1972,14 @@ int srsran_ue_ul_gpu_tx_batch(uint32_t nof_ue, const srsran_ue_ul_gpu_entry_t* e
     if (!g0->d_ptx.reserve(pdesc.size() * sizeof(PucchTxUe)) ||
         hipMemcpyAsync(g0->d_ptx, pdesc.data(), pdesc.size() * sizeof(PucchTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
         pucch_tx_launch((const PucchTxUe*)g0->d_ptx.get(), (uint32_t)pdesc.size(), st) != hipSuccess) {
+      return SRSRAN_ERROR;
+    }
+  }
+  if (!sdesc.empty()) {  // every SRS of every cell in one launch, after the channels it shares a grid with
+    UeUlGpu* g0 = (UeUlGpu*)entries[0].q->gpu;
+    if (!g0->d_stx.reserve(sdesc.size() * sizeof(SrsTxUe)) ||
+        hipMemcpyAsync(g0->d_stx, sdesc.data(), sdesc.size() * sizeof(SrsTxUe), hipMemcpyHostToDevice, st) != hipSuccess ||
+        srs_tx_launch((const SrsTxUe*)g0->d_stx.get(), (uint32_t)sdesc.size(), st) != hipSuccess) {
       return SRSRAN_ERROR;
     }
   }
@@ -1627,8 +2083,11 @@ int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_
   const size_t sf_len = q->cell.nof_prb ? q->fft.sf_sz : 0;
   if (!cfg->grant_available) {
     const srsran_uci_cfg_t& pu = cfg->ul_cfg.pucch.uci_cfg;
-    if ((srsran_uci_cfg_total_ack(&pu) > 0 || pu.cqi.data_enable || pu.cqi.ri_len > 0 || data->uci.scheduling_request) &&
-        cfg->cc_idx == 0) {  // PUCCH, over the PCell only (ue_ul.c:642-648): a batch of one
+    const bool pucch = (srsran_uci_cfg_total_ack(&pu) > 0 || pu.cqi.data_enable || pu.cqi.ri_len > 0 ||
+                        data->uci.scheduling_request) &&
+                       cfg->cc_idx == 0;
+    // PUCCH, over the PCell only (ue_ul.c:642-648), else the SRS alone (649-651): a batch of one
+    if (pucch || srs_tx_enabled(cfg->ul_cfg.srs, sf->tti)) {
       hipStream_t st = sch_stream(&q->pusch.ul_sch);
       if (!g->hop_ok || !q->out_buffer || !g->d_io.reserve(sf_len * sizeof(cf_t))) {
         return SRSRAN_ERROR;
@@ -1643,9 +2102,6 @@ int srsran_ue_ul_encode(srsran_ue_ul_t* q, srsran_ul_sf_cfg_t* sf, srsran_ue_ul_
         ret = SRSRAN_ERROR;
       }
       return ret == SRSRAN_SUCCESS ? 1 : SRSRAN_ERROR;
-    }
-    if (srs_in_subframe(cfg, sf->tti)) {
-      return SRSRAN_ERROR;
     }
     if (sf_len && q->out_buffer) {
       memset(q->out_buffer, 0, sf_len * sizeof(cf_t));

@@ -20,41 +20,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "chest_ul_dev.h"
 #include "dft_mixed_dev.h"
 #include "pusch_kernel.h"
 #include "stage_timing.h"
 
 namespace srsran_amd {
-
-// sum over the block of NV floats per thread; every thread gets the totals
-template <int NV>
-__device__ __forceinline__ void block_sum(float (&v)[NV], float* red)
-{
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      v[k] += __shfl_xor(v[k], off, 64);
-    }
-  }
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-      red[w * NV + k] = v[k];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-    float s = 0.f;
-    for (int i = 0; i < nw; i++) {
-      s += red[i * NV + k];
-    }
-    v[k] = s;
-  }
-}
 
 // ---------------------------------------------------------------- channel estimation
 // 16 waves a UE: 78 UEs are 78 workgroups, so each one's 2 M pilots and 14 M estimate stores spread over more
@@ -88,18 +59,7 @@ __global__ __launch_bounds__(CHUL_THREADS) void chest_ul_kernel(const PuschUe* _
     const c2       x = mk(p[j]);
     c2             a = x;
     if (u.smooth) {
-      c2 l, r;
-      if (j == 0) {
-        l = sub(scl(mk(p[1]), 3.0f), scl(mk(p[0]), 2.0f));
-      } else {
-        l = mk(p[j - 1]);
-      }
-      if (j == M - 1) {
-        r = sub(scl(mk(p[M - 1]), 3.0f), scl(mk(p[M - 2]), 2.0f));
-      } else {
-        r = mk(p[j + 1]);
-      }
-      a = add(add(scl(l, f0), scl(x, f1)), scl(r, f2));
+      a = smooth3(p, j, M, f0, f1, f2);
       const c2 d = sub(a, x);
       acc[3 + s] += d.r * d.r + d.i * d.i;
     }
@@ -123,18 +83,10 @@ __global__ __launch_bounds__(CHUL_THREADS) void chest_ul_kernel(const PuschUe* _
     float ta = 0.0f;
     if (u.meas_ta) {
       for (int s = 0; s < 2; s++) {
-        const float f = (float)((double)-atan2f(acc[8 + 2 * s], acc[7 + 2 * s]) * 0.31830988618379067154 * 0.5);
-        ta += f / 2.0f;
+        ta += freq_from_corr(acc[7 + 2 * s], acc[8 + 2 * s]) / 2.0f;
       }
     }
-    if (isnormal(ta)) {
-      ta /= 15e3f;
-      ta *= 1e6f;
-      ta = roundf(ta * 10.0f) / 10.0f;
-    } else {
-      ta = 0.0f;
-    }
-    o.ta_us = ta;
+    o.ta_us = ta_us_from_freq(ta);
     if (u.smooth) {
       float power = acc[3] / (float)M;
       power += acc[4] / (float)M;

@@ -23,6 +23,12 @@ class srsran_refsignal_dmrs_pusch_cfg_t(ctypes.Structure):
                 ("sequence_hopping_en", ctypes.c_bool)]
 
 
+class srsran_refsignal_srs_cfg_t(ctypes.Structure):
+    _fields_ = [("subframe_config", u32), ("bw_cfg", u32), ("simul_ack", ctypes.c_bool), ("B", u32), ("b_hop", u32),
+                ("n_srs", u32), ("I_srs", u32), ("k_tc", u32), ("n_rrc", u32), ("dedicated_enabled", ctypes.c_bool),
+                ("common_enabled", ctypes.c_bool), ("configured", ctypes.c_bool)]
+
+
 class srsran_chest_ul_res_t(ctypes.Structure):
     _fields_ = [("ce", ctypes.POINTER(ctypes.c_float)), ("nof_re", u32), ("noise_estimate", _f),
                 ("noise_estimate_dbFs", _f), ("rsrp", _f), ("rsrp_dBfs", _f), ("epre", _f), ("epre_dBfs", _f),
@@ -49,6 +55,16 @@ class srsran_pusch_gpu_ue_t(ctypes.Structure):
     _fields_ = [("chest", ctypes.POINTER(srsran_chest_ul_t)), ("sf", ctypes.POINTER(srsran_ul_sf_cfg_t)),
                 ("cfg", ctypes.POINTER(srsran_pusch_cfg_t)), ("d_sf_symbols", ctypes.c_void_p), ("new_data", u32)]
 
+
+class srsran_chest_ul_gpu_srs_t(ctypes.Structure):
+    _fields_ = [("q", ctypes.POINTER(srsran_chest_ul_t)), ("sf", ctypes.POINTER(srsran_ul_sf_cfg_t)),
+                ("cfg", ctypes.POINTER(srsran_refsignal_srs_cfg_t)),
+                ("pusch_cfg", ctypes.POINTER(srsran_refsignal_dmrs_pusch_cfg_t)), ("d_sf_symbols", ctypes.c_void_p),
+                ("res", ctypes.POINTER(srsran_chest_ul_res_t))]
+
+
+SCALARS = ("noise_estimate", "noise_estimate_dbFs", "rsrp", "rsrp_dBfs", "epre", "epre_dBfs", "snr", "snr_db", "cfo_hz",
+           "ta_us")
 
 _bound = False
 
@@ -77,6 +93,11 @@ def lib():
             "srsran_chest_ul_set_cell": ([CH, srsran_cell_t], ctypes.c_int),
             "srsran_chest_ul_pregen": ([CH, DM, ctypes.c_void_p], None),
             "srsran_chest_ul_estimate_pusch": ([CH, SF, CFG, _cfp, RES], ctypes.c_int),
+            "srsran_chest_ul_estimate_srs": ([CH, SF, ctypes.POINTER(srsran_refsignal_srs_cfg_t), DM, _cfp, RES],
+                                             ctypes.c_int),
+            "srsran_chest_ul_gpu_estimate_srs_batch": ([u32, ctypes.POINTER(srsran_chest_ul_gpu_srs_t), ctypes.c_void_p],
+                                                       ctypes.c_int),
+            "srsran_chest_ul_gpu_srs_result": ([RES], ctypes.c_int),
             "srsran_pusch_init_enb": ([PU, u32], ctypes.c_int),
             "srsran_pusch_free": ([PU], None),
             "srsran_pusch_set_cell": ([PU, srsran_cell_t], ctypes.c_int),
@@ -109,7 +130,7 @@ def dmrs(cell, cfg, nof_prb, sf_idx, n_dmrs):
 class ChestUl:
     """srsran_chest_ul_t + one srsran_chest_ul_res_t"""
 
-    def __init__(self, cell, dmrs_cfg, max_prb=100):
+    def __init__(self, cell, dmrs_cfg, max_prb=100, srs_cfg=None):
         self.cell = cell
         self.q = srsran_chest_ul_t()
         self.res = srsran_chest_ul_res_t()
@@ -117,7 +138,8 @@ class ChestUl:
         assert L.srsran_chest_ul_init(ctypes.byref(self.q), max_prb) == 0
         assert L.srsran_chest_ul_res_init(ctypes.byref(self.res), max_prb) == 0
         assert L.srsran_chest_ul_set_cell(ctypes.byref(self.q), cell) == 0
-        L.srsran_chest_ul_pregen(ctypes.byref(self.q), ctypes.byref(dmrs_cfg), None)
+        L.srsran_chest_ul_pregen(ctypes.byref(self.q), ctypes.byref(dmrs_cfg),
+                                 None if srs_cfg is None else ctypes.cast(ctypes.pointer(srs_cfg), ctypes.c_void_p))
         assert self.q.dmrs_signal_configured
 
     def estimate(self, sf, cfg, grid):
@@ -126,6 +148,20 @@ class ChestUl:
                                                    g.ctypes.data, ctypes.byref(self.res))
         return ret
 
+    def estimate_srs(self, sf, srs_cfg, dmrs_cfg, grid, res=None):
+        """srsran_chest_ul_estimate_srs on a host grid into self.res (or res)"""
+        g = np.ascontiguousarray(grid, dtype=np.complex64)
+        return lib().srsran_chest_ul_estimate_srs(ctypes.byref(self.q), ctypes.byref(sf), ctypes.byref(srs_cfg),
+                                                  ctypes.byref(dmrs_cfg), g.ctypes.data,
+                                                  ctypes.byref(self.res if res is None else res))
+
+    def scalars(self, res=None):
+        r = self.res if res is None else res
+        return {k: float(getattr(r, k)) for k in SCALARS}
+
+    def set_identity(self):
+        lib().srsran_chest_ul_res_set_identity(ctypes.byref(self.res))
+
     def ce(self, n):
         return np.ctypeslib.as_array(self.res.ce, shape=(2 * n,)).view(np.complex64).copy()
 
@@ -133,6 +169,20 @@ class ChestUl:
         if self.q.gpu:
             lib().srsran_chest_ul_res_free(ctypes.byref(self.res))
             lib().srsran_chest_ul_free(ctypes.byref(self.q))
+
+
+def estimate_srs_batch(entries, stream=None):
+    """srsran_chest_ul_gpu_estimate_srs_batch; entries: (ChestUl, sf, srs cfg, dmrs cfg, device grid pointer, res)"""
+    arr = (srsran_chest_ul_gpu_srs_t * len(entries))()
+    for e, (ch, sf, cfg, d, ptr, res) in zip(arr, entries):
+        e.q, e.sf, e.cfg, e.pusch_cfg = ctypes.pointer(ch.q), ctypes.pointer(sf), ctypes.pointer(cfg), ctypes.pointer(d)
+        e.d_sf_symbols, e.res = ptr, ctypes.pointer(res)
+    return lib().srsran_chest_ul_gpu_estimate_srs_batch(len(entries), arr, stream)
+
+
+def srs_result(res):
+    """srsran_chest_ul_gpu_srs_result after the stream has drained"""
+    return lib().srsran_chest_ul_gpu_srs_result(ctypes.byref(res))
 
 
 class Pusch:

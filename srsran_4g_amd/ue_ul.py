@@ -1,12 +1,13 @@
 """Python mirror of the UE uplink transmit C API (include/srsran_ue_ul.h with the transmit additions of
 srsran_sch.h / srsran_pusch.h): srsran_ulsch_encode, srsran_pusch_encode, the DMRS put, srsran_ue_ul_encode and the
-device batch srsran_ue_ul_gpu_tx_batch.  No CPU fallback: everything but the UCI coding runs the HIP kernels."""
+device batch srsran_ue_ul_gpu_tx_batch, and the host helpers of the sounding reference signal.  No CPU fallback: everything but the UCI coding runs the HIP kernels."""
 import ctypes
 
 import numpy as np
 
 from .pucch import srsran_pucch_cfg_t, srsran_uci_cfg_t
-from .pusch import (lib as _pusch_lib, srsran_pusch_t, srsran_refsignal_dmrs_pusch_cfg_t, srsran_ul_sf_cfg_t)
+from .pusch import (lib as _pusch_lib, srsran_pusch_t, srsran_refsignal_dmrs_pusch_cfg_t, srsran_refsignal_srs_cfg_t,
+                    srsran_ul_sf_cfg_t)
 from .sch import Sch, _memcpy_d2h, srsran_pusch_cfg_t, srsran_sch_t, srsran_uci_value_t
 from .ue_dl import srsran_cell_t, srsran_ofdm_t
 
@@ -19,12 +20,6 @@ NORMALIZE_AUTO, NORMALIZE_FORCE_AMPLITUDE = 0, 1
 
 class srsran_pusch_data_t(ctypes.Structure):
     _fields_ = [("ptr", ctypes.c_void_p), ("uci", srsran_uci_value_t)]
-
-
-class srsran_refsignal_srs_cfg_t(ctypes.Structure):
-    _fields_ = [("subframe_config", u32), ("bw_cfg", u32), ("simul_ack", _b), ("B", u32), ("b_hop", u32),
-                ("n_srs", u32), ("I_srs", u32), ("k_tc", u32), ("n_rrc", u32), ("dedicated_enabled", _b),
-                ("common_enabled", _b), ("configured", _b)]
 
 
 class srsran_pusch_hopping_cfg_t(ctypes.Structure):
@@ -78,6 +73,8 @@ def lib():
         CFG = ctypes.POINTER(srsran_pusch_cfg_t)
         UCFG = ctypes.POINTER(srsran_ue_ul_cfg_t)
         DATA = ctypes.POINTER(srsran_pusch_data_t)
+        SRS = ctypes.POINTER(srsran_refsignal_srs_cfg_t)
+        CELL = ctypes.POINTER(srsran_cell_t)
         sig = {
             "srsran_ulsch_encode": ([ctypes.POINTER(srsran_sch_t), CFG, P, ctypes.POINTER(srsran_uci_value_t), P, P],
                                     ctypes.c_int),
@@ -101,6 +98,18 @@ def lib():
             "srsran_ue_ul_gen_sr": ([UCFG, SF, ctypes.POINTER(srsran_uci_data_t), _b], _b),
             "srsran_refsignal_srs_pucch_shortened_cfg": ([SF, ctypes.POINTER(srsran_refsignal_srs_cfg_t),
                                                           ctypes.POINTER(srsran_pucch_cfg_t)], None),
+            "srsran_refsignal_srs_cfg_isvalid": ([SRS, u32], _b),
+            "srsran_refsignal_srs_send_cs": ([u32, u32], ctypes.c_int),
+            "srsran_refsignal_srs_send_ue": ([u32, u32], ctypes.c_int),
+            "srsran_refsignal_srs_rb_start_cs": ([u32, u32], u32),
+            "srsran_refsignal_srs_rb_L_cs": ([u32, u32], u32),
+            "srsran_refsignal_srs_M_sc_cell": ([CELL, SRS], u32),
+            "srsran_refsignal_srs_k0_cell": ([CELL, SRS, u32], u32),
+            "srsran_refsignal_srs_pusch_shortened_cfg": ([CELL, SF, SRS, CFG], None),
+            "srsran_refsignal_srs_gen_cell": ([CELL, SRS, ctypes.POINTER(srsran_refsignal_dmrs_pusch_cfg_t), u32, P],
+                                              ctypes.c_int),
+            "srsran_refsignal_srs_put_cell": ([CELL, SRS, u32, P, P], ctypes.c_int),
+            "srsran_refsignal_srs_get_cell": ([CELL, SRS, u32, P, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -142,6 +151,47 @@ def dmrs_put(cell, cfg, r, grid):
     r = np.ascontiguousarray(r, dtype=np.complex64)
     return lib().srsran_refsignal_dmrs_pusch_put_cell(ctypes.byref(cell), ctypes.byref(cfg), r.ctypes.data,
                                                       grid.ctypes.data)
+
+
+def srs_cfg_isvalid(srs, nof_prb):
+    return bool(lib().srsran_refsignal_srs_cfg_isvalid(ctypes.byref(srs), nof_prb))
+
+
+def srs_M_sc(cell, srs):
+    return lib().srsran_refsignal_srs_M_sc_cell(ctypes.byref(cell), ctypes.byref(srs))
+
+
+def srs_k0(cell, srs, tti):
+    return lib().srsran_refsignal_srs_k0_cell(ctypes.byref(cell), ctypes.byref(srs), tti)
+
+
+def srs_pusch_shortened(cell, sf, srs, pusch_cfg):
+    """srsran_refsignal_srs_pusch_shortened_cfg: writes and returns sf.shortened"""
+    lib().srsran_refsignal_srs_pusch_shortened_cfg(ctypes.byref(cell), ctypes.byref(sf), ctypes.byref(srs),
+                                                   ctypes.byref(pusch_cfg))
+    return bool(sf.shortened)
+
+
+def srs_gen(cell, srs, dmrs, sf_idx):
+    """srsran_refsignal_srs_gen_cell -> (ret, the 2 M_sc values of the subframe's two slots)"""
+    r = np.zeros(2 * max(srs_M_sc(cell, srs), 1), np.complex64)
+    ret = lib().srsran_refsignal_srs_gen_cell(ctypes.byref(cell), ctypes.byref(srs), ctypes.byref(dmrs), sf_idx,
+                                              r.ctypes.data)
+    return ret, r
+
+
+def srs_put(cell, srs, tti, r, grid):
+    """srsran_refsignal_srs_put_cell on a host grid (complex64, modified in place)"""
+    r = np.ascontiguousarray(r, dtype=np.complex64)
+    return lib().srsran_refsignal_srs_put_cell(ctypes.byref(cell), ctypes.byref(srs), tti, r.ctypes.data, grid.ctypes.data)
+
+
+def srs_get(cell, srs, tti, grid):
+    """srsran_refsignal_srs_get_cell -> (ret, the M_sc comb REs of the last symbol)"""
+    r = np.zeros(max(srs_M_sc(cell, srs), 1), np.complex64)
+    g = np.ascontiguousarray(grid, dtype=np.complex64)
+    ret = lib().srsran_refsignal_srs_get_cell(ctypes.byref(cell), ctypes.byref(srs), tti, r.ctypes.data, g.ctypes.data)
+    return ret, r
 
 
 class PuschUe:
@@ -196,7 +246,7 @@ class UeUl:
         if lib().srsran_ue_ul_gpu_last(ctypes.byref(self.q), ctypes.byref(ds), ctypes.byref(nb), ctypes.byref(dd),
                                        ctypes.byref(nr), ctypes.byref(dg), ctypes.byref(ng)):
             raise RuntimeError("srsran_ue_ul_gpu_last: no encode to read")
-        # after a PUCCH subframe nof_bits = nof_re = 0: the grid alone
+        # after a PUCCH or an SRS-only subframe nof_bits = nof_re = 0: the grid alone
         s = torch.empty(nb.value // 8, dtype=torch.uint8)
         d = torch.empty(2 * nr.value, dtype=torch.float32)
         g = torch.empty(2 * ng.value, dtype=torch.float32)
@@ -225,4 +275,5 @@ def tx_batch(entries, stream=None):
     return lib().srsran_ue_ul_gpu_tx_batch(len(entries), arr, stream)
 
 
-__all__ = ["Sch", "PuschUe", "UeUl", "tx_batch", "ulsch_encode", "dmrs_put", "srsran_ue_ul_cfg_t"]
+__all__ = ["Sch", "PuschUe", "UeUl", "tx_batch", "ulsch_encode", "dmrs_put", "srsran_ue_ul_cfg_t", "srs_cfg_isvalid",
+           "srs_M_sc", "srs_k0", "srs_pusch_shortened", "srs_gen", "srs_put", "srs_get"]

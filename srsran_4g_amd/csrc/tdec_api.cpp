@@ -743,7 +743,7 @@ namespace {
 constexpr int kPoolStreams = 4;
 // Device descriptors of one fused multi-size launch (per decoder class).
 struct MultiDesc {
-  PinBuf<char> h_stage;          // pinned: TdecArgs[n] | first[n]
+  PinBuf<char> h_stage;          // pinned: TdecArgs[n] | ck_off[n] (uint64) | first[n]
   DevBuf<char> d_stage;          // same capacity
   hipEvent_t copied  = nullptr;  // the last upload from h_stage finished
   bool       used    = false;
@@ -755,7 +755,13 @@ struct StreamPool {
   hipEvent_t  done[kPoolStreams];
   hipEvent_t  fork;
   hipEvent_t  large_done;  // the 16-step part's largest sizes finished (gates the other classes, tdec_gate())
-  MultiDesc   md[6];  // launch entries: 16 (16-step, large K), 16 (16-step, mid K), 16 (8-step part), 8, generic x 2
+  // launch entries: 16 (16-step, top residency tier), 16 (16-step, the other large K), 16 (16-step, mid K),
+  // 16 (8-step part), 8, generic x 2
+  MultiDesc   md[7];
+  // window checkpoints of the fused 16-step launches (tdecs_ck_geo.h): grow-only, one region a workgroup, every
+  // launch of a call its own part of it; the launches that use it all run on s[0] (or, serial mode, on s[0] too)
+  DevBuf<uint8_t>       d_ck;
+  std::map<size_t, int> wg_per_cu;  // the fused 16-step kernel's workgroups a CU by LDS bytes a workgroup (queried once)
 };
 std::mutex               g_pool_mu;
 std::vector<StreamPool*> g_pools;
@@ -821,14 +827,15 @@ uint32_t gen_cut()
 }
 
 // The 16-step part of a fused 16-sub-block class is cut once more at this K (SRSRAN_AMD_TDEC_MIDCUT, read once;
-// 0 = one launch): its sizes above run first with K = 6144's LDS a workgroup (two a CU, nothing else fits beside
-// them), its sizes up to the cut follow on the same stream with their own, smaller LDS figure -- room beside them
-// for the 8-step part's, the 8-sub-block class's and the generic class's workgroups.
+// 0 = no mid part): its sizes above run first, cut by residency (srsran_tdec_gpu_run_multi: three or four workgroups
+// a CU at two waves a SIMD, nothing else fits beside them), its sizes up to the cut follow on the same stream with
+// their own, smaller LDS figure -- room beside them for the 8-step part's, the 8-sub-block class's and the generic
+// class's workgroups.  2048 from the sweep with the two-wave kernel (HISTORY.md; 3072 at one wave a SIMD).
 uint32_t tdec_midcut()
 {
   static const uint32_t c = [] {
     const char* e = getenv("SRSRAN_AMD_TDEC_MIDCUT");
-    return e ? (uint32_t)atoi(e) : 3072u;
+    return e ? (uint32_t)atoi(e) : 2048u;
   }();
   return c;
 }
@@ -842,6 +849,16 @@ bool tdec_gate()
     return e ? atoi(e) != 0 : true;
   }();
   return g;
+}
+
+// Workgroups of the fused 16-step kernel that a CU holds at `lds` bytes each (0: the query failed).
+int fused16_wg_per_cu(StreamPool* p, size_t lds)
+{
+  auto it = p->wg_per_cu.find(lds);
+  if (it == p->wg_per_cu.end()) {
+    it = p->wg_per_cu.emplace(lds, tdecs16::multi_wg_per_cu(lds)).first;
+  }
+  return it->second;
 }
 
 // Rough serial-latency model used only to order launches (longest first).
@@ -908,19 +925,44 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
   // tdecs_w8_fused_max_k(): its sizes up to there run the 8-step-window build (fewer registers and
   // little LDS a workgroup: their workgroups can share SIMDs with the large sizes' ones) as their own
   // launch.
-  // launch entries: 16 (16-step, K > mid cut), 16 (16-step, cut < K <= mid cut), 16 (8-step part), 8, generic x 2
-  const int      cls_nsb[6] = {16, 16, 16, 8, 1, 1};
-  const int      cls_st[6]  = {0, 0, 1, 2, 3, 3};  // pool stream of each entry (both 16-step parts: one stream)
+  // The fused 16-step kernel runs two waves a SIMD and keeps its checkpoints out of LDS, so the workgroups a CU holds
+  // depend on the launch's LDS figure: the sizes above the mid cut are cut once more where that residency changes
+  // (three a CU at K = 6144, four -- the register limit -- from about K = 4600 down), each part with the LDS of
+  // its own largest K.
+  // launch entries: 16 (16-step, K > mid cut, the residency of the largest K), 16 (16-step, K > mid cut, the rest),
+  // 16 (16-step, cut < K <= mid cut), 16 (8-step part), 8, generic x 2
+  const int      cls_nsb[7] = {16, 16, 16, 16, 8, 1, 1};
+  const int      cls_st[7]  = {0, 0, 0, 1, 2, 3, 3};  // pool stream of each entry (the 16-step parts: one stream)
   const uint32_t midcut     = tdec_midcut();
+  const uint32_t cut        = std::max(tdecs_w8_max_k(), tdecs_w8_fused_max_k());
   bool           gated      = false;
-  bool           mid_run    = false;  // entry 1 launched: the 16-step part was cut at midcut
-  for (int ci = 0; ci < 6 && ret == SRSRAN_SUCCESS; ci++) {
-    if (ci == 1 && hipEventRecord(p->large_done, p->s[0]) != hipSuccess) {  // behind the large sizes (entry 0)
+  bool           mid_run    = false;  // entry 2 launched: the 16-step part was cut at midcut
+  // the checkpoint scratch of this call's fused 16-step launches, allocated before the first of them
+  uint64_t ck_need = 0, ck_used = 0;
+  const Config* top16 = nullptr;  // the largest 16-step size
+  for (uint32_t g = 0; g < nof_groups && layout_sb; g++) {
+    if (cfg[g]->nsb == 16 && cfg[g]->proto.K > cut && nof_cb[g] > 0) {
+      TdecArgs a = cfg[g]->proto;
+      a.ncb      = nof_cb[g];
+      ck_need += tdecs16::multi_ck_bytes(a);
+      top16 = top16 && top16->proto.K > a.K ? top16 : cfg[g];
+    }
+  }
+  if (ck_need > p->d_ck.cap()) {
+    hipStreamSynchronize(p->s[0]);  // an earlier call's launches may still use the old block
+    if (!p->d_ck.reserve(ck_need)) {
+      return SRSRAN_ERROR;
+    }
+  }
+  auto residency = [&](const Config* c) { return fused16_wg_per_cu(p, tdecs16::multi_lds_bytes(c->proto)); };
+  const int top_res = top16 ? residency(top16) : 0;
+  for (int ci = 0; ci < 7 && ret == SRSRAN_SUCCESS; ci++) {
+    if (ci == 2 && hipEventRecord(p->large_done, p->s[0]) != hipSuccess) {  // behind the large sizes (entries 0, 1)
       ret = SRSRAN_ERROR;
       break;
     }
     // with the 16-step part cut at midcut, the other classes start when its large sizes are done, beside the mid part
-    gated = ci >= 2 && mid_run && tdec_gate() && multi_mode() != 2;
+    gated = ci >= 3 && mid_run && tdec_gate() && multi_mode() != 2;
     std::vector<uint32_t> gs;
     uint32_t              cls_cb = 0;  // blocks of the whole class (decides the kernel)
     for (uint32_t i = 0; i < nof_groups; i++) {
@@ -937,26 +979,29 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
                      : !layout_sb                   ? 0
                      : cls_nsb[ci] == 16            ? tdec16_choice(cls_cb)
                                                     : (cls_cb >= tdec8s_min_cb() ? 2 : 0);
-    const uint32_t cut = std::max(tdecs_w8_max_k(), tdecs_w8_fused_max_k());
-    if (cls_nsb[ci] == 16 && kind == 2) {  // entry 0: K above the mid cut; entry 1: up to it; entry 2: up to the cut
-      const uint32_t lo = ci == 0 ? std::max(cut, midcut) : ci == 1 ? cut : 0;
-      const uint32_t hi = ci == 0 ? UINT32_MAX : ci == 1 ? std::max(cut, midcut) : cut;
+    if (cls_nsb[ci] == 16 && kind == 2) {
+      // entries 0, 1: K above the mid cut, by residency; entry 2: up to the mid cut; entry 3: up to the cut
+      const uint32_t lo = ci <= 1 ? std::max(cut, midcut) : ci == 2 ? cut : 0;
+      const uint32_t hi = ci <= 1 ? UINT32_MAX : ci == 2 ? std::max(cut, midcut) : cut;
       gs.erase(std::remove_if(gs.begin(), gs.end(),
-                              [&](uint32_t g) { return !(cfg[g]->proto.K > lo && cfg[g]->proto.K <= hi); }),
+                              [&](uint32_t g) {
+                                const uint32_t K = cfg[g]->proto.K;
+                                return !(K > lo && K <= hi) || (ci <= 1 && (residency(cfg[g]) == top_res) != (ci == 0));
+                              }),
                gs.end());
-    } else if (ci == 1 || ci == 2) {
-      gs.clear();  // no 16-step mid part / 8-step part outside the single-lane class
-    } else if (ci >= 4 && kind == 0 && gen_cut() > 0) {  // generic quad: K above the cut, then the rest
-      const bool small = ci == 5;
+    } else if (ci >= 1 && ci <= 3) {
+      gs.clear();  // no second large part / 16-step mid part / 8-step part outside the single-lane class
+    } else if (ci >= 5 && kind == 0 && gen_cut() > 0) {  // generic quad: K above the cut, then the rest
+      const bool small = ci == 6;
       gs.erase(std::remove_if(gs.begin(), gs.end(), [&](uint32_t g) { return (cfg[g]->proto.K <= gen_cut()) != small; }),
                gs.end());
-    } else if (ci == 5) {
+    } else if (ci == 6) {
       gs.clear();  // one generic launch
     }
     if (gs.empty()) {
       continue;
     }
-    mid_run        = mid_run || ci == 1;
+    mid_run        = mid_run || ci == 2;
     hipStream_t st = p->s[multi_mode() == 2 ? 0 : cls_st[ci]];
     if (gated && st != p->s[0] && hipStreamWaitEvent(st, p->large_done, 0) != hipSuccess) {
       ret = SRSRAN_ERROR;
@@ -973,12 +1018,14 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
       kmax = std::max(kmax, cfg[g]->proto.K);
     }
     const bool w8  = kind == 2 && nsbc > 1 && kmax <= (nsbc == 16 ? cut : tdecs_w8_max_k());  // 8-step windows
+    const bool gck = kind == 2 && nsbc == 16 && !w8;  // the fused 16-step kernel: checkpoints in p->d_ck
     const int  cpw  = kind == 2   ? (nsbc == 16 ? tdecs16::cpw() : nsbc == 8 ? tdecs8::cpw() : tdecs1::cpw())
                       : kind == 1 ? tdec16_cpw()
                                   : tdec_cpw(nsbc);
     const size_t   n     = gs.size();
     const size_t   abyte = n * sizeof(TdecArgs);
-    const size_t   need  = abyte + n * sizeof(uint32_t);
+    const size_t   kbyte = n * sizeof(uint64_t);
+    const size_t   need  = abyte + kbyte + n * sizeof(uint32_t);
     MultiDesc&     m     = p->md[ci];
     if (m.used) {
       hipEventSynchronize(m.copied);
@@ -990,7 +1037,8 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
       }
     }
     TdecArgs* ha    = reinterpret_cast<TdecArgs*>(m.h_stage.get());
-    uint32_t* hf    = reinterpret_cast<uint32_t*>(m.h_stage + abyte);
+    uint64_t* hk    = reinterpret_cast<uint64_t*>(m.h_stage + abyte);  // bytes to each group's part of p->d_ck
+    uint32_t* hf    = reinterpret_cast<uint32_t*>(m.h_stage + abyte + kbyte);
     uint32_t  nblk  = 0;
     size_t    lds   = 0;
     for (size_t k = 0; k < n; k++) {
@@ -1009,10 +1057,14 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
       a.tfwd_nat       = c->d_tfwd_nat;
       a.trev_nat       = c->d_trev_nat;
       a.state          = nullptr;
+      hk[k] = ck_used;
+      if (gck) {
+        ck_used += tdecs16::multi_ck_bytes(a);
+      }
       ha[k]            = a;
       hf[k]            = nblk;
       nblk += (nof_cb[g] + cpw - 1) / cpw;
-      lds = std::max(lds, kind == 2   ? (nsbc == 16  ? (w8 ? tdecs16w8::lds_bytes(a) : tdecs16::lds_bytes(a))
+      lds = std::max(lds, kind == 2   ? (nsbc == 16  ? (w8 ? tdecs16w8::lds_bytes(a) : tdecs16::multi_lds_bytes(a))
                                          : nsbc == 8 ? (w8 ? tdecs8w8::lds_bytes(a) : tdecs8::lds_bytes(a))
                                                      : tdecs1::lds_bytes(a))
                           : kind == 1 ? tdec16_lds_bytes(a)
@@ -1024,9 +1076,11 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
     hipEventRecord(m.copied, st);
     m.used = true;
     const TdecArgs* dg = reinterpret_cast<const TdecArgs*>(m.d_stage.get());
-    const uint32_t* df = reinterpret_cast<const uint32_t*>(m.d_stage + abyte);
+    const uint64_t* dk = reinterpret_cast<const uint64_t*>(m.d_stage + abyte);
+    const uint32_t* df = reinterpret_cast<const uint32_t*>(m.d_stage + abyte + kbyte);
     if ((kind == 2   ? (nsbc == 16  ? (w8 ? tdecs16w8::multi_launch(dg, df, (int)n, nblk, lds, st)
-                                          : tdecs16::multi_launch(dg, df, (int)n, nblk, lds, st))
+                                          : tdecs16::multi_launch_ck(dg, df, dk, (int)n, nblk, lds, p->d_ck.get(),
+                                                                     p->d_ck.cap(), st))
                         : nsbc == 8 ? (w8 ? tdecs8w8::multi_launch(dg, df, (int)n, nblk, lds, st)
                                           : tdecs8::multi_launch(dg, df, (int)n, nblk, lds, st))
                                     : tdecs1::multi_launch(dg, df, (int)n, nblk, lds, st))

@@ -93,6 +93,16 @@ SRSRAN_TDECS_API(tdecs16w8)  // the same built with 8-step windows (fewer regist
 SRSRAN_TDECS_API(tdecs8w8)
 SRSRAN_TDECS_API(tdecs1)  // tdec1s_kernel.hip: the generic decoder (K <= 400), one lane per block and side
 #undef SRSRAN_TDECS_API
+namespace tdecs16 {
+// The fused launch keeps its window checkpoints in a device scratch (tdecs_ck_geo.h): multi_launch_ck instead of
+// multi_launch, with d_ck_off[g] = bytes from d_ck to group g's part (multi_ck_bytes of it) and ck_bytes = the bytes
+// of d_ck.  LDS of a group's workgroup (no checkpoints); workgroups a CU holds at `lds` bytes each.
+hipError_t multi_launch_ck(const TdecArgs* d_groups, const uint32_t* d_first, const uint64_t* d_ck_off, int ngroups,
+                           uint32_t nblocks, size_t lds, uint8_t* d_ck, uint64_t ck_bytes, hipStream_t stream);
+size_t     multi_lds_bytes(const TdecArgs& a);
+uint64_t   multi_ck_bytes(const TdecArgs& a);
+int        multi_wg_per_cu(size_t lds);
+}  // namespace tdecs16
 #ifdef TDECS_STAMPS  // diagnostic build (Makefile `stamps`): phase-boundary clock stamps of the single-lane kernels
 namespace tdecs16 { hipError_t set_stamps(void* d_buf); }
 namespace tdecs8 { hipError_t set_stamps(void* d_buf); }

@@ -32,6 +32,7 @@
 #include "crc24_dev.h"
 #include "stage_timing.h"
 #include "tdec_kernel.h"
+#include "tdecs_ck_geo.h"
 
 #ifndef TDECS_NSB
 #define TDECS_NSB 16
@@ -57,6 +58,13 @@
 #define TDECS_NAME "tdec8sw8_"
 #else
 #error "TDECS_NSB must be 16 or 8, TDECS_W 16 or 8"
+#endif
+// the fused launch of the 16-sub-block class on 16-step windows keeps its window checkpoints in a device scratch
+// instead of LDS and is built for two waves a SIMD (tdecs_ck_geo.h)
+#if TDECS_NSB == 16 && TDECS_W == 16
+#define TDECS_GCK 1
+#else
+#define TDECS_GCK 0
 #endif
 
 namespace srsran_amd {
@@ -218,11 +226,11 @@ __device__ __forceinline__ St trellis(const short* xt, const short* yt)
 struct Geo {
   int s_dw, ck_dw, bits_dw, cb_dw;
 };
-__host__ __device__ __forceinline__ Geo geo(int K, int Ls, int M, bool slot)
+__host__ __device__ __forceinline__ Geo geo(int K, int Ls, int M, bool slot, bool gck = false)
 {
   Geo g;
   g.s_dw    = (NSB * Ls + 1) / 2;
-  g.ck_dw   = M * NSB * 4;
+  g.ck_dw   = gck ? 0 : M * NSB * 4;  // gck: the checkpoints live in the device scratch (tdecs_ck_geo.h)
   g.bits_dw = slot ? (NSB * Ls + 31) / 32 + 1 : (K / 8 + 3) / 4;
   g.cb_dw   = g.s_dw + g.ck_dw + g.bits_dw + 2;
   return g;
@@ -258,15 +266,31 @@ struct Lane {
   lshort    S;     // this block's S (LDS)
   lshort    Ssb;   // S + s * Ls: this lane's sub-block
   uint4*    CK;    // this block's checkpoints (LDS), [M][NSB]
+  rsrc_t    rck;   // GCK: this workgroup's region of the checkpoint scratch, [M][64 lanes][16 B]
+  uint32_t  ckv;   // GCK: this lane's bytes into a window's row of it
   uint32_t* BITS;  // this block's decision bitmap (LDS)
 };
 
+// GCK (the fused 16-step launches): a checkpoint is one 16-byte store / load of the lane, a wave's 64 a contiguous
+// kilobyte of the workgroup's scratch region; out-of-range stores are dropped, loads return zero (buffer resource).
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+template <bool GCK>
 __device__ __forceinline__ void ck_put(const Lane& c, int m, const St& p)
 {
-  c.CK[m * NSB + c.s] = make_uint4(v2u(p.a), v2u(p.b), v2u(p.c), v2u(p.d));
+  if (GCK) {
+    const v4u v = {v2u(p.a), v2u(p.b), v2u(p.c), v2u(p.d)};
+    __builtin_amdgcn_raw_buffer_store_b128(v, c.rck, c.ckv, tdecs_ck_row(m), 0);
+  } else {
+    c.CK[m * NSB + c.s] = make_uint4(v2u(p.a), v2u(p.b), v2u(p.c), v2u(p.d));
+  }
 }
+template <bool GCK>
 __device__ __forceinline__ St ck_get(const Lane& c, int m)
 {
+  if (GCK) {
+    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(c.rck, c.ckv, tdecs_ck_row(m), 0);
+    return St{u2v(v.x), u2v(v.y), u2v(v.z), u2v(v.w)};
+  }
   const uint4 v = c.CK[m * NSB + c.s];
   return St{u2v(v.x), u2v(v.y), u2v(v.z), u2v(v.w)};
 }
@@ -300,6 +324,10 @@ __device__ __forceinline__ uint32_t pin(uint32_t v)
 {
   asm volatile("" : "+v"(v));
   return v;
+}
+[[maybe_unused]] __device__ __forceinline__ St pin(const St& p)  // used by the two-wave build only
+{
+  return St{u2v(pin(v2u(p.a))), u2v(pin(v2u(p.b))), u2v(pin(v2u(p.c))), u2v(pin(v2u(p.d)))};
 }
 
 // The LLR o of position k: S update (vec_sub, wraps) and, when the half-iteration's decision is
@@ -369,7 +397,7 @@ __device__ __forceinline__ uint32_t nat_byte(const uint32_t* bits, int L, int Ls
 
 // Phase-2 alpha side, window at t0 >= W: beta[t0+1 .. cc] recomputed from the stored beta at
 // cc = min(t0 + W, L) (checkpoint), then alpha + LLR of t0 .. cc-1.
-template <bool D2, int BITS, bool FULL>
+template <bool D2, int BITS, bool FULL, bool GCK = false>
 __device__ __forceinline__ St alpha_llr_window(const Lane& c, St P, int t0, St Pb, const uint32_t* xw,
                                                const uint32_t* aux)
 {
@@ -392,7 +420,7 @@ __device__ __forceinline__ St alpha_llr_window(const Lane& c, St P, int t0, St P
 #pragma unroll
   for (int i = 0; i < W; i++) {
     if (FULL || t0 + i < L) {
-      const Cand  cd = cand(P, bm(xw[i]));
+      const Cand  cd = cand(P, bm(GCK ? pin(xw[i]) : xw[i]));
       const short o  = llr(cd, bw[i]);
       P              = next<false>(cd);
       if ((i & 1) == 0) P = norm(P);  // t0 >= W: every even position
@@ -407,7 +435,7 @@ __device__ __forceinline__ St alpha_llr_window(const Lane& c, St P, int t0, St P
 
 // Phase-1 beta side, window at t0 >= W: backward over t0+W-1 .. t0 (FULL) or L-1 .. t0; Bst = the
 // stored beta at t0, which is the checkpoint of window t0/W - 1 when `store`.
-template <bool FULL>
+template <bool FULL, bool GCK = false>
 __device__ __forceinline__ St beta_window(const Lane& c, St P, int t0, bool store, St& Bst, const uint32_t* xw)
 {
 #pragma unroll
@@ -417,7 +445,7 @@ __device__ __forceinline__ St beta_window(const Lane& c, St P, int t0, bool stor
       if (i == 0) {
         Bst = P;
         if (store) {
-          ck_put(c, t0 / W - 1, P);
+          ck_put<GCK>(c, t0 / W - 1, P);
         }
       }
       if ((i & 1) == 0) P = norm(P);
@@ -526,7 +554,24 @@ struct Pipe {
 };
 
 // One constituent MAP decode of this lane's sub-block; wave 0 = alpha side, wave 1 = beta side.
-template <bool D2, int BITS>
+// GCK: the checkpoints go through the device scratch (ck_put / ck_get).
+// Phase 1 stores them, the other wave loads them in phase 2: release / acquire fences of workgroup scope around the
+// phase barrier, and no phase-2 checkpoint load before it.  The first phase-2 window's checkpoint (the one the other
+// side wrote last) is loaded right behind the barrier, one exposed L2 round trip a half-iteration; every later one
+// is loaded a window ahead, behind the window's input loads, and has landed by the window's one wait.
+template <bool GCK>
+__device__ __forceinline__ void phase_barrier()
+{
+  if (GCK) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  }
+  __syncthreads();
+  if (GCK) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+}
+
+template <bool D2, int BITS, bool GCK = false>
 __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
 {
   (void)st0;  // first stamp index of this half-iteration (TDECS_STAMPS builds)
@@ -575,7 +620,7 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
     for (int ma = 0; ma < h; ma++) {
       const int t0 = ma * W;
       pp.next(c, t0 + W, xw, aux);  // h < Ma: window h exists
-      ck_put(c, ma, P);
+      ck_put<GCK>(c, ma, P);
 #pragma unroll
       for (int i = 0; i < W; i++) {
         P = step<false>(P, xw[i]);
@@ -584,19 +629,30 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
       pp.taken(c);
     }
     TDECS_STAMP(st0 + 2);
-    __syncthreads();
+    phase_barrier<GCK>();
     TDECS_STAMP(st0 + 3);
     // phase 2: windows [h, Ma): beta recomputed from the checkpoint above the window, then alpha + LLR
     const int tlast = (Ma - 1) * W;
+    St        ckc;  // GCK: the current window's checkpoint
+    if (GCK) {
+      ckc = ck_get<true>(c, h);
+    }
 #pragma unroll 1
     for (int ma = h; ma < Mfull; ma++) {
       pp.next(c, min(ma * W + W, tlast), xw, aux);
-      P = alpha_llr_window<D2, BITS, true>(c, P, ma * W, ck_get(c, ma), xw, aux);
+      St ckn;
+      if (GCK) {
+        ckn = ck_get<true>(c, min(ma + 1, Ma - 1));
+      }
+      P = alpha_llr_window<D2, BITS, true, GCK>(c, P, ma * W, GCK ? ckc : ck_get<false>(c, ma), xw, aux);
       pp.taken(c);
+      if (GCK) {
+        ckc = ckn;
+      }
     }
     if (Ma > Mfull) {
       pp.template next<true>(c, 0, xw, aux);
-      alpha_llr_window<D2, BITS, false>(c, P, Mfull * W, ck_get(c, Mfull), xw, aux);
+      alpha_llr_window<D2, BITS, false, GCK>(c, P, Mfull * W, GCK ? ckc : ck_get<false>(c, Mfull), xw, aux);
     }
     TDECS_STAMP(st0 + 4);
   } else {
@@ -637,30 +693,37 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
       }
     }
     const int mtop = Ma - 1;
-    ck_put(c, mtop, P);  // beta[L]
+    ck_put<GCK>(c, mtop, P);  // beta[L]
     St Bst = P;  // stored (pre-normalisation) beta of the position above the current window
     // phase 1: windows [h, Ma) from the top (the top one maybe partial)
     if (Ma > Mfull) {
       pp.next(c, (mtop - 1) * W, xw, aux);  // Ma >= 4
-      P = beta_window<false>(c, P, mtop * W, mtop > h, Bst, xw);
+      P = beta_window<false, GCK>(c, P, mtop * W, mtop > h, Bst, xw);
       pp.taken(c);
     }
 #pragma unroll 1
     for (int mb = Mfull - 1; mb >= h; mb--) {
       pp.next(c, mb * W - W, xw, aux);  // mb >= h >= 1
-      P = beta_window<true>(c, P, mb * W, mb > h, Bst, xw);
+      P = beta_window<true, GCK>(c, P, mb * W, mb > h, Bst, xw);
       pp.taken(c);
     }
     TDECS_STAMP(st0 + 2);
-    __syncthreads();
+    phase_barrier<GCK>();
     TDECS_STAMP(st0 + 3);
     // phase 2: windows [0, h) from the top: alpha recomputed from the entry checkpoint, then
     // beta backwards with the LLR of every position
+    St ckc;  // GCK: the current window's checkpoint
+    if (GCK) {
+      ckc = ck_get<true>(c, h - 1);
+    }
 #pragma unroll 1
     for (int mb = h - 1; mb >= 0; mb--) {
       const int t0 = mb * W;
       pp.next(c, max(t0 - W, 0), xw, aux);
-      St Pa = ck_get(c, mb);
+      St Pa = GCK ? ckc : ck_get<false>(c, mb);
+      if (GCK) {
+        ckc = ck_get<true>(c, max(mb - 1, 0));
+      }
       St aw[W];  // alpha entering each position (candidates rebuilt at LLR time)
 #pragma unroll
       for (int i = 0; i < W; i++) {
@@ -673,7 +736,12 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
       uint32_t wbits = 0;
 #pragma unroll
       for (int i = W - 1; i >= 0; i--) {
-        const short o = llr(cand(aw[i], bm(xw[i])), Bst);
+        short o;
+        if constexpr (GCK) {  // rebuilt here as written, not kept from the loop above (96 registers)
+          o = llr(cand(pin(aw[i]), bm(pin(xw[i]))), Bst);
+        } else {
+          o = llr(cand(aw[i], bm(xw[i])), Bst);
+        }
         P             = step<true>(P, xw[i]);
         Bst           = P;
         if (nrm(t0, i)) P = norm(P);
@@ -690,8 +758,9 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
 
 }  // namespace
 
-template <bool ES>
-__device__ __forceinline__ void body(const TdecArgs& a, int bid)
+// GCK: ck / ck_bytes = the group's part of the checkpoint scratch
+template <bool ES, bool GCK = false>
+__device__ __forceinline__ void body(const TdecArgs& a, int bid, uint8_t* ck = nullptr, uint64_t ck_bytes = 0)
 {
   constexpr int NT = 128;  // threads: the alpha and the beta wave
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -704,7 +773,7 @@ __device__ __forceinline__ void body(const TdecArgs& a, int bid)
   const int L    = (int)a.L;
   const int Ls   = (int)a.Ls;
   const int M    = (L + W - 1) / W;
-  const Geo g    = geo(K, Ls, M, ES);
+  const Geo g    = geo(K, Ls, M, ES, GCK);
   const int cb   = bid * CPWG + cbw;
   const int cbl  = cb < (int)a.ncb ? cb : (int)a.ncb - 1;
   const bool live = cb < (int)a.ncb && (!ES || a.cbs[cbl].slot != TDEC_PAD_SLOT);
@@ -740,6 +809,10 @@ __device__ __forceinline__ void body(const TdecArgs& a, int bid)
   c.Ssb  = c.S + c.s * Ls;
   c.CK   = reinterpret_cast<uint4*>(base + g.s_dw);
   c.BITS = base + g.s_dw + g.ck_dw;
+  if constexpr (GCK) {  // this workgroup's region of the group's checkpoint scratch, and no byte beyond it
+    c.rck = make_rsrc(ck + tdecs_ck_wg_off((uint32_t)L, (uint32_t)bid), tdecs_ck_wg_avail((uint32_t)L, (uint32_t)bid, ck_bytes));
+    c.ckv = tdecs_ck_lane((uint32_t)lane);
+  }
   uint32_t* RED = c.BITS + g.bits_dw;
 
   if constexpr (ES) {
@@ -769,15 +842,15 @@ __device__ __forceinline__ void body(const TdecArgs& a, int bid)
     constexpr int BM   = ES ? 2 : 1;  // the bit layout (emit)
     if (hi & 1) {
       if (bits) {
-        map16s<true, BM>(c, wave, 5 * hi);
+        map16s<true, BM, GCK>(c, wave, 5 * hi);
       } else {
-        map16s<true, 0>(c, wave, 5 * hi);
+        map16s<true, 0, GCK>(c, wave, 5 * hi);
       }
     } else {
       if (bits) {
-        map16s<false, BM>(c, wave, 5 * hi);
+        map16s<false, BM, GCK>(c, wave, 5 * hi);
       } else {
-        map16s<false, 0>(c, wave, 5 * hi);
+        map16s<false, 0, GCK>(c, wave, 5 * hi);
       }
     }
     __syncthreads();
@@ -864,8 +937,13 @@ __global__ __launch_bounds__(128, 1) void TDECS_K(kernel)(TdecArgs a)
   body<ES>(a, blockIdx.x);
 }
 
-__global__ __launch_bounds__(128, 1) void TDECS_K(multi_kernel)(const TdecArgs* __restrict__ groups,
-                                                            const uint32_t* __restrict__ first, int ngroups)
+__global__ __launch_bounds__(128, TDECS_GCK ? 2 : 1) void TDECS_K(multi_kernel)(const TdecArgs* __restrict__ groups,
+                                                            const uint32_t* __restrict__ first, int ngroups
+#if TDECS_GCK
+                                                            , const uint64_t* __restrict__ ck_off, uint8_t* ck,
+                                                            uint64_t ck_bytes
+#endif
+)
 {
   if constexpr (NSB == 16 && W == 16) {
     // the large sizes of a cut all-188 class are the step's critical path: their waves win the VALU
@@ -885,7 +963,14 @@ __global__ __launch_bounds__(128, 1) void TDECS_K(multi_kernel)(const TdecArgs* 
     }
   }
   const TdecArgs a = groups[lo];
+#if TDECS_GCK
+  // the group's part of the scratch: its workgroups' regions, clipped to the buffer
+  const uint64_t off  = ck_off[lo];
+  const uint64_t part = tdecs_ck_group_bytes(a.L, (a.ncb + CPWG - 1) / CPWG);
+  body<false, true>(a, (int)(b - first[lo]), ck + off, off >= ck_bytes ? 0 : min(part, ck_bytes - off));
+#else
   body<false>(a, (int)(b - first[lo]));
+#endif
 }
 
 size_t lds_bytes(const TdecArgs& a)
@@ -893,6 +978,25 @@ size_t lds_bytes(const TdecArgs& a)
   const Geo g = geo((int)a.K, (int)a.Ls, (int)((a.L + W - 1) / W), a.cbs != nullptr);
   return (size_t)CPWG * g.cb_dw * 4;
 }
+
+#if TDECS_GCK
+// the fused launch's workgroup: LDS, and the bytes of the checkpoint scratch a group of a.ncb blocks needs
+size_t multi_lds_bytes(const TdecArgs& a)
+{
+  const Geo g = geo((int)a.K, (int)a.Ls, (int)((a.L + W - 1) / W), false, true);
+  return (size_t)CPWG * g.cb_dw * 4;
+}
+uint64_t multi_ck_bytes(const TdecArgs& a)
+{
+  return tdecs_ck_group_bytes(a.L, (a.ncb + CPWG - 1) / CPWG);
+}
+// workgroups of the fused kernel a CU holds at `lds` bytes each (registers, LDS: the runtime's occupancy query)
+int multi_wg_per_cu(size_t lds)
+{
+  int n = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, TDECS_K(multi_kernel), 128, lds) == hipSuccess ? n : 0;
+}
+#endif
 
 int cpw() { return CPWG; }
 
@@ -917,10 +1021,29 @@ hipError_t multi_launch(const TdecArgs* d_groups, const uint32_t* d_first, int n
   if (ngroups == 0 || nblocks == 0) {
     return hipSuccess;
   }
+#if TDECS_GCK
+  return hipErrorInvalidValue;  // this build's fused kernel needs its checkpoint scratch: multi_launch_ck
+#else
   tdec_set_last_kernel(TDECS_NAME "multi_kernel");
   hipLaunchKernelGGL(TDECS_K(multi_kernel), dim3(nblocks), dim3(128), lds, stream, d_groups, d_first, ngroups);
   return hipGetLastError();
+#endif
 }
+
+#if TDECS_GCK
+hipError_t multi_launch_ck(const TdecArgs* d_groups, const uint32_t* d_first, const uint64_t* d_ck_off, int ngroups,
+                           uint32_t nblocks, size_t lds, uint8_t* d_ck, uint64_t ck_bytes, hipStream_t stream)
+{
+  StageScope timing_scope(ST_TDEC, stream);
+  if (ngroups == 0 || nblocks == 0) {
+    return hipSuccess;
+  }
+  tdec_set_last_kernel(TDECS_NAME "multi_kernel");
+  hipLaunchKernelGGL(TDECS_K(multi_kernel), dim3(nblocks), dim3(128), lds, stream, d_groups, d_first, ngroups, d_ck_off,
+                     d_ck, ck_bytes);
+  return hipGetLastError();
+}
+#endif
 
 #ifdef TDECS_STAMPS
 hipError_t set_stamps(void* d_buf)

@@ -16,6 +16,7 @@
 #include "../../include/srsran_ue_dl.h"
 #include "chest_kernel.h"
 #include "dev_buf.h"
+#include "lte_seq_host.h"
 #include "pdsch_internal.h"
 #include "ofdm_kernel.h"
 
@@ -26,23 +27,6 @@ namespace {
 // phy_common.c:31-35: non-standard (3/4) sampling rates unless built with FORCE_STANDARD_RATE;
 // srsUE and the reference tests opt in with srsran_use_standard_symbol_size(true).
 bool g_standard_rates = false;
-
-// LTE Gold sequence c(n), n = 0..len-1 (36.211 7.2, Nc = 1600)
-void gold(uint32_t c_init, uint8_t* c, uint32_t len)
-{
-  uint32_t x1 = 1, x2 = c_init & 0x7FFFFFFFu;
-  auto     s1 = [](uint32_t s) { return (s >> 1) ^ (((s ^ (s >> 3)) & 1u) << 30); };
-  auto     s2 = [](uint32_t s) { return (s >> 1) ^ (((s ^ (s >> 1) ^ (s >> 2) ^ (s >> 3)) & 1u) << 30); };
-  for (int n = 0; n < 1600; n++) {
-    x1 = s1(x1);
-    x2 = s2(x2);
-  }
-  for (uint32_t n = 0; n < len; n++) {
-    c[n] = (uint8_t)((x1 ^ x2) & 1u);
-    x1   = s1(x1);
-    x2   = s2(x2);
-  }
-}
 
 struct ChestGpu {
   hipStream_t stream  = nullptr;
@@ -83,7 +67,7 @@ std::vector<float2> mbsfn_pilots(const srsran_cell_t& cell, uint32_t area)
   for (uint32_t sf = 0; sf < 10; sf++) {
     for (uint32_t l = 0; l < 3; l++) {
       const uint32_t lp = (2 + 4 * l) % 6, slot = l ? 2 * sf + 1 : 2 * sf;
-      gold(512 * (7 * (slot + 1) + lp + 1) * (2 * area + 1) + area, c.data(), 20 * 110);
+      gold_bytes(512 * (7 * (slot + 1) + lp + 1) * (2 * area + 1) + area, c.data(), 20 * 110);
       for (uint32_t i = 0; i < 6 * N; i++) {
         const uint32_t mp = i + 3 * (110 - N);
         t[(sf * 3 + l) * 6 * N + i] = make_float2((1 - 2 * (float)c[2 * mp]) * a, (1 - 2 * (float)c[2 * mp + 1]) * a);
@@ -381,7 +365,7 @@ int srsran_chest_dl_set_cell(srsran_chest_dl_t* q, srsran_cell_t cell)
       for (uint32_t l = 0; l < nsym_slot; l++) {
         const uint32_t lp     = pp == 0 ? (l ? nsymb - 3 : 0) : 1;  // srsran_refsignal_cs_nsymbol
         const uint32_t c_init = 1024 * (7 * (ns + 1) + lp + 1) * (2 * cell.id + 1) + 2 * cell.id + N_cp;
-        gold(c_init, c.data(), 4 * 110);
+        gold_bytes(c_init, c.data(), 4 * 110);
         float2* dst = &h[(ns / 2) * kPilotsPerSf + pp * 4 * CHEST_MAX_NREF +
                          2 * cell.nof_prb * ((ns % 2) * nsym_slot + l)];
         for (uint32_t i = 0; i < 2 * cell.nof_prb; i++) {

@@ -24,14 +24,9 @@
 #include "dev_buf.h"
 #include "ldpc_internal.h"
 #include "nr_sch_kernel.h"
+#include "sch_internal.h"
 
 using namespace srsran_amd;
-
-namespace srsran_amd {
-uint8_t* softbuffer_dflags(srsran_softbuffer_rx_t* q);
-uint8_t* softbuffer_ddata(srsran_softbuffer_rx_t* q);
-uint32_t softbuffer_data_stride(srsran_softbuffer_rx_t* q);
-}  // namespace srsran_amd
 
 namespace {
 

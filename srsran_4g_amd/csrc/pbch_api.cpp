@@ -13,6 +13,7 @@
 
 #include "../../include/srsran_pbch.h"
 #include "dev_buf.h"
+#include "lte_seq_host.h"
 #include "pbch_kernel.h"
 #include "pdsch_internal.h"
 
@@ -67,21 +68,6 @@ struct PbchGpu {
   DevBuf<float>    d_mib_res;
   DevBuf<uint32_t> d_mib_sf;  // the subframe index the batch estimator reads: 0
 };
-
-// srsran_sequence_LTE_pr (sequence.c, 36.211 7.2): len bits of the Gold sequence of c_init, packed
-void gold_bits(uint32_t c_init, uint32_t len, uint32_t* out)
-{
-  uint32_t x1 = 1, x2 = c_init & 0x7fffffffu;
-  for (uint32_t n = 0; n < 1600 + len; n++) {
-    if (n >= 1600 && ((x1 ^ x2) & 1u)) {
-      out[(n - 1600) >> 5] |= 1u << ((n - 1600) & 31);
-    }
-    const uint32_t f1 = ((x1 >> 3) ^ x1) & 1u;
-    const uint32_t f2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 1u;
-    x1                = (x1 >> 1) | (f1 << 30);
-    x2                = (x2 >> 1) | (f2 << 30);
-  }
-}
 
 void pbch_free_gpu(PbchGpu* g)
 {
@@ -342,7 +328,7 @@ int srsran_pbch_set_cell(srsran_pbch_t* q, srsran_cell_t cell)
   if (q->cell.id != cell.id || q->cell.nof_prb == 0) {  // pbch.c:247-252
     q->cell = cell;
     std::vector<uint32_t> seq(kSeqWords, 0u);
-    gold_bits(cell.id, cell.cp == SRSRAN_CP_NORM ? 1920 : 1728, seq.data());
+    gold_words(cell.id, seq.data(), cell.cp == SRSRAN_CP_NORM ? 1920 : 1728);
     if (hipMemcpy(g->d_seq, seq.data(), kSeqWords * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
       return SRSRAN_ERROR;
     }

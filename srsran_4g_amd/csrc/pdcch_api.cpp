@@ -16,28 +16,12 @@
 #include "../../include/srsran_pdcch.h"
 #include "dev_buf.h"
 #include "eq_kernel.h"
+#include "lte_seq_host.h"
 #include "pdcch_kernel.h"
 
 using namespace srsran_amd;
 
 namespace {
-
-// ---------------- Gold sequence (36.211 7.2; sequence.c:48-102) ----------------
-void gold_bits(uint32_t c_init, uint32_t len, std::vector<uint32_t>& words)
-{
-  words.assign((len + 31) / 32, 0u);
-  uint32_t x1 = 1, x2 = c_init & 0x7fffffffu;  // 31-bit registers, bit n = x(n)
-  for (uint32_t n = 0; n < 1600 + len; n++) {
-    if (n >= 1600) {
-      const uint32_t c = (x1 ^ x2) & 1u;
-      words[(n - 1600) >> 5] |= c << ((n - 1600) & 31);
-    }
-    const uint32_t f1 = ((x1 >> 3) ^ x1) & 1u;
-    const uint32_t f2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 1u;
-    x1                = (x1 >> 1) | (f1 << 30);
-    x2                = (x2 >> 1) | (f2 << 30);
-  }
-}
 
 // ---------------- REG tables (regs.c) ----------------
 struct Reg {
@@ -445,9 +429,7 @@ int srsran_pcfich_set_cell(srsran_pcfich_t* q, srsran_regs_t* regs, srsran_cell_
   q->cell    = cell;
   std::vector<uint32_t> seq(10);
   for (uint32_t sf = 0; sf < 10; sf++) {  // srsran_sequence_pcfich (sequences.c:38-41)
-    std::vector<uint32_t> w;
-    gold_bits((sf + 1) * (2 * cell.id + 1) * 512 + cell.id, 32, w);
-    seq[sf] = w[0];
+    gold_words((sf + 1) * (2 * cell.id + 1) * 512 + cell.id, &seq[sf], 32);
   }
   if (hipMemcpyAsync(g->d_seq, seq.data(), 10 * sizeof(uint32_t), hipMemcpyHostToDevice, g->stream) != hipSuccess ||
       hipMemcpyAsync(g->d_idx, regs->pcfich_re, 16 * sizeof(uint32_t), hipMemcpyHostToDevice, g->stream) !=
@@ -556,11 +538,9 @@ int srsran_pdcch_set_cell(srsran_pdcch_t* q, srsran_regs_t* regs, srsran_cell_t 
   CtrlGpu*       g     = (CtrlGpu*)q->gpu;
   const uint32_t nbits = 8 * regs->pdcch_nregs[2];  // sequence for the largest control region (pdcch.c:160-169)
   g->seq_words         = (nbits + 31) / 32;
-  std::vector<uint32_t> all;
+  std::vector<uint32_t> all(10 * (size_t)g->seq_words);
   for (uint32_t sf = 0; sf < 10; sf++) {  // srsran_sequence_pdcch (sequences.c:54-57)
-    std::vector<uint32_t> w;
-    gold_bits(sf * 512 + cell.id, nbits, w);
-    all.insert(all.end(), w.begin(), w.end());
+    gold_words(sf * 512 + cell.id, all.data() + sf * g->seq_words, nbits);
   }
   if (hipMemcpyAsync(g->d_seq, all.data(), all.size() * sizeof(uint32_t), hipMemcpyHostToDevice, g->stream) !=
           hipSuccess ||

@@ -12,6 +12,7 @@
 
 #include "../../include/srsran_phich.h"
 #include "dev_buf.h"
+#include "lte_seq_host.h"
 #include "phich_kernel.h"
 
 using namespace srsran_amd;
@@ -34,22 +35,6 @@ struct PhichGpu {
   DevBuf<PhichOut> d_out;
   uint32_t  nre    = 0;  // of the cell the scratch was sized for
 };
-
-// srsran_sequence_LTE_pr (sequence.c, 36.211 7.2): the first 12 bits of the Gold sequence of c_init
-uint32_t gold12(uint32_t c_init)
-{
-  uint32_t x1 = 1, x2 = c_init & 0x7fffffffu, out = 0;
-  for (uint32_t n = 0; n < 1600 + 12; n++) {
-    if (n >= 1600) {
-      out |= ((x1 ^ x2) & 1u) << (n - 1600);
-    }
-    const uint32_t f1 = ((x1 >> 3) ^ x1) & 1u;
-    const uint32_t f2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 1u;
-    x1                = (x1 >> 1) | (f1 << 30);
-    x2                = (x2 >> 1) | (f2 << 30);
-  }
-  return out;
-}
 
 bool is_ext(const srsran_phich_t* q) { return q->cell.cp == SRSRAN_CP_EXT; }
 
@@ -219,7 +204,7 @@ int srsran_phich_set_cell(srsran_phich_t* q, srsran_regs_t* regs, srsran_cell_t 
   PhichGpu* g = (PhichGpu*)q->gpu;
   q->cell     = cell;
   for (uint32_t sf = 0; sf < 10; sf++) {  // srsran_sequence_phich(2 * sf, cell.id)
-    g->seq[sf] = gold12((sf + 1) * (2 * cell.id + 1) * 512 + cell.id);
+    gold_words((sf + 1) * (2 * cell.id + 1) * 512 + cell.id, &g->seq[sf], 12);
   }
   srsran_phich_set_regs(q, regs);
   return q->regs ? SRSRAN_SUCCESS : SRSRAN_ERROR;

@@ -1,6 +1,6 @@
 // srsran_4g_amd/csrc/pucch_api.cpp -- C-ABI of the PUCCH receive path (include/srsran_pucch.h):
 // the resource helpers of pucch.c:943-1264, pucch_proc.c and refsignal_ul.c:360-429 restated on the
-// host, srsran_chest_ul_estimate_pucch (chest_ul.c:462-610), srsran_pucch_decode (pucch.c:797-872)
+// host (the per-cell tables are in refsignal_ul_api.cpp), srsran_chest_ul_estimate_pucch (chest_ul.c:462-610), srsran_pucch_decode (pucch.c:797-872)
 // and srsran_pucch_gpu_get_batch (the sequence of enb_ul.c:156-273 for many UEs), over the kernel
 // of pucch_kernel.hip; and the transmit side of the UE (pucch.c:583-623, 768-794, refsignal_ul.c:432-552):
 // srsran_pucch_init_ue, srsran_pucch_encode and the DMRS generation / mapping over pucch_tx_kernel.hip.
@@ -11,139 +11,29 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "../../include/srsran_pucch.h"
 #include "dev_buf.h"
+#include "lte_seq_host.h"
 #include "pucch_kernel.h"
 #include "pucch_tx_kernel.h"
-
-namespace srsran_amd {
-hipStream_t chest_ul_stream(srsran_chest_ul_t* q);
-void*       chest_ul_scratch(srsran_chest_ul_t* q, size_t bytes);
-void        chest_ul_res_host_changed(srsran_chest_ul_res_t* res);
-}  // namespace srsran_amd
+#include "ul_internal.h"
 
 using namespace srsran_amd;
 
 namespace {
 
-#include "zc_tables.inc"
-
-typedef uint32_t ncs_table_t[SRSRAN_NSLOTS_X_FRAME][SRSRAN_CP_NORM_NSYMB];
-
-uint32_t nsymb_slot(srsran_cp_t cp) { return cp == SRSRAN_CP_NORM ? 7u : 6u; }
-bool     cell_valid(const srsran_cell_t& c) { return c.id < 504 && c.nof_ports >= 1 && c.nof_ports <= 4 && c.nof_prb >= 6 && c.nof_prb <= SRSRAN_MAX_PRB; }
 bool     is_f1(srsran_pucch_format_t f) { return f == SRSRAN_PUCCH_FORMAT_1 || f == SRSRAN_PUCCH_FORMAT_1A || f == SRSRAN_PUCCH_FORMAT_1B; }
 bool     is_f2(srsran_pucch_format_t f) { return f == SRSRAN_PUCCH_FORMAT_2 || f == SRSRAN_PUCCH_FORMAT_2A || f == SRSRAN_PUCCH_FORMAT_2B; }
-
-// ---- LTE Gold sequence (36.211 7.2, Nc = 1600)
-uint32_t step_x1(uint32_t s) { return (s >> 1) ^ (((s ^ (s >> 3)) & 1u) << 30); }
-uint32_t step_x2(uint32_t s) { return (s >> 1) ^ (((s ^ (s >> 1) ^ (s >> 2) ^ (s >> 3)) & 1u) << 30); }
-
-// The states after the 1600 warm-up steps: x1's is a constant, x2's is linear in c_init, so it is the
-// xor of the columns of the set seed bits.
-struct GoldJump {
-  uint32_t x1;
-  uint32_t col[31];
-  GoldJump()
-  {
-    x1 = 1;
-    for (int n = 0; n < 1600; n++) {
-      x1 = step_x1(x1);
-    }
-    for (int b = 0; b < 31; b++) {
-      uint32_t x2 = 1u << b;
-      for (int n = 0; n < 1600; n++) {
-        x2 = step_x2(x2);
-      }
-      col[b] = x2;
-    }
-  }
-};
-
-void gold(uint32_t c_init, uint8_t* c, uint32_t len)
-{
-  static const GoldJump jump;
-  uint32_t              x1 = jump.x1, x2 = 0;
-  for (int b = 0; b < 31; b++) {
-    if ((c_init >> b) & 1u) {
-      x2 ^= jump.col[b];
-    }
-  }
-  for (uint32_t n = 0; n < len; n++) {
-    c[n] = (uint8_t)((x1 ^ x2) & 1u);
-    x1   = step_x1(x1);
-    x2   = step_x2(x2);
-  }
-}
 
 // the first 48 bits of srsran_sequence_pucch (sequences.c:169-172), bit i of the result is c(i)
 uint64_t pucch_scrambling(uint16_t rnti, uint32_t tti, uint32_t cell_id)
 {
   const uint32_t nslot = 2 * (tti % 10);
-  uint8_t        c[48];
-  gold((((nslot / 2) + 1) * (2 * cell_id + 1) << 16) + rnti, c, 48);
-  uint64_t v = 0;
-  for (int i = 0; i < 48; i++) {
-    v |= (uint64_t)c[i] << i;
-  }
-  return v;
-}
-
-void n_cs_cell_gen(const srsran_cell_t& cell, ncs_table_t n_cs_cell)
-{
-  const uint32_t       nsym = nsymb_slot(cell.cp);
-  std::vector<uint8_t> c(8 * nsym * SRSRAN_NSLOTS_X_FRAME);
-  gold(cell.id, c.data(), (uint32_t)c.size());
-  for (uint32_t ns = 0; ns < SRSRAN_NSLOTS_X_FRAME; ns++) {
-    for (uint32_t l = 0; l < nsym; l++) {
-      uint32_t v = 0;
-      for (uint32_t i = 0; i < 8; i++) {
-        v += (uint32_t)c[8 * nsym * ns + 8 * l + i] << i;
-      }
-      n_cs_cell[ns][l] = v;
-    }
-  }
-}
-
-// srsran_group_hopping_f_gh (refsignal_ul.c:140-156)
-void f_gh_gen(uint32_t cell_id, uint32_t f_gh[SRSRAN_NSLOTS_X_FRAME])
-{
-  uint8_t c[8 * SRSRAN_NSLOTS_X_FRAME];
-  gold(cell_id / 30, c, sizeof(c));
-  for (uint32_t ns = 0; ns < SRSRAN_NSLOTS_X_FRAME; ns++) {
-    f_gh[ns] = 0;
-    for (int i = 0; i < 8; i++) {
-      f_gh[ns] += (uint32_t)c[8 * ns + i] << i;
-    }
-  }
-}
-
-struct CellTables {
-  uint32_t n_cs_cell[SRSRAN_NSLOTS_X_FRAME][SRSRAN_CP_NORM_NSYMB];
-  uint32_t f_gh[SRSRAN_NSLOTS_X_FRAME];
-};
-
-// per (cell id, CP) tables, computed once per process; entries are never removed
-const CellTables* cell_tables(const srsran_cell_t& cell)
-{
-  static std::mutex                      mtx;
-  static std::map<uint32_t, CellTables*> cache;
-  std::lock_guard<std::mutex>            lock(mtx);
-  const uint32_t                         key = cell.id * 2 + (cell.cp == SRSRAN_CP_NORM ? 0 : 1);
-  auto                                   it  = cache.find(key);
-  if (it != cache.end()) {
-    return it->second;
-  }
-  CellTables* t = new CellTables();
-  memset(t, 0, sizeof(*t));
-  n_cs_cell_gen(cell, t->n_cs_cell);
-  f_gh_gen(cell.id, t->f_gh);
-  cache[key] = t;
-  return t;
+  uint32_t       w[2];
+  gold_words((((nslot / 2) + 1) * (2 * cell_id + 1) << 16) + rnti, w, 48);
+  return (uint64_t)w[1] << 32 | w[0];
 }
 
 // ---- cyclic shifts (pucch.c:1149-1234); the public alpha is 2 pi n_cs / 12
@@ -258,7 +148,7 @@ int build_cand(const srsran_cell_t&      cell,
       return SRSRAN_ERROR;
     }
     const uint32_t u = ((cfg->group_hopping_en ? t.f_gh[ns] : 0) + (cell.id % 30)) % 30;
-    memcpy(c.phi[s], kZcPhi12[u], 12);
+    memcpy(c.phi[s], zc_phi12(u), 12);
     for (uint32_t m = 0; m < c.n_rs; m++) {
       const uint32_t l = c.rs_sym[m];
       if (is_f1(f)) {
@@ -304,9 +194,7 @@ int build_cand(const srsran_cell_t&      cell,
     c.filt[0]     = chest->smooth_filter[0];
     c.filt[1]     = chest->smooth_filter[1];
     c.filt[2]     = chest->smooth_filter[2];
-    const float w = chest->smooth_filter[0];
-    const float a = (float)(7.419 * w * w + 0.1117 * w - 0.005387);  // chest_ul.c:452-456
-    c.noise_div   = (double)a * 0.8;
+    c.noise_div   = chest_ul_noise_div(chest->smooth_filter[0]);  // chest_ul.c:452-456
   }
   return SRSRAN_SUCCESS;
 }
@@ -1277,7 +1165,7 @@ int build_tx(const srsran_cell_t& cell, const srsran_ul_sf_cfg_t* sf, srsran_puc
 
 namespace srsran_amd {
 
-// srsran_pucch_encode up to the kernel, for the UE uplink (pusch_api.cpp): the descriptor of cfg->format /
+// srsran_pucch_encode up to the kernel, for the UE uplink (ue_ul_api.cpp): the descriptor of cfg->format /
 // cfg->n_pucch carrying *uci, pointers left null.  Writes cfg->pucch2_drs_bits for 2a / 2b.
 int pucch_tx_prepare(const srsran_cell_t&      cell,
                      const srsran_ul_sf_cfg_t* sf,

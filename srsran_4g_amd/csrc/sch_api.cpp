@@ -29,8 +29,8 @@
 #include "enc_kernel.h"
 #include "uci_kernel.h"
 #include "pdsch_internal.h"
-#include "ulsch_batch.h"
-#include "pusch_tx_internal.h"
+#include "sch_internal.h"
+#include "tdec_internal.h"
 #include "stage_copy.h"
 #include "stage_timing.h"
 
@@ -1962,7 +1962,7 @@ int ulsch_decode_dev(srsran_sch_t* q, srsran_pusch_cfg_t* cfg, int16_t* d_q, con
   return ulsch_decode_impl(q, cfg, nullptr, d_q, nullptr, nullptr, nullptr, d_c, data, uci_data);
 }
 
-// Batched srsran_ulsch_decode (ulsch_batch.h): the same stages as ulsch_decode_impl, each one launch
+// Batched srsran_ulsch_decode (sch_internal.h): the same stages as ulsch_decode_impl, each one launch
 // over every UE of the batch, and one decode_tb batch for all their transport blocks.
 int ulsch_decode_batch_dev(srsran_sch_t* q, uint32_t n, UlschBatchUe* ues, const uint8_t* d_data_base,
                            size_t data_bytes, hipStream_t st)
@@ -2176,14 +2176,7 @@ int srsran_ulsch_gpu_decode_batch(srsran_sch_t*                q,
   return srsran_dlsch_gpu_decode_batch(q, nof_tb, dl.data(), d_result, d_avg_noi, stream);
 }
 
-
 // ---------------- DL-SCH transmit (sch.c:240-359, 621-652) ----------------
-}  // extern "C"
-namespace srsran_amd {
-bool rm_fwd_table(uint32_t cb_idx, uint32_t rv, const uint16_t** d_fwd, uint32_t* N);
-void qpp_coeffs(uint32_t idx, uint32_t* f1, uint32_t* f2);
-}  // namespace srsran_amd
-extern "C" {
 
 // encode_tb_off's split of the E bits over the blocks (sch.c:271-305); the K2 blocks come first.  Appends the TB's
 // code block descriptors: c.e holds the byte offset e_off + (bits before the block) and c.tb_crc the TB index t, both

@@ -26,6 +26,7 @@
 #include "devkey.h"
 #include "tdec_kernel.h"
 #include "tdec8bit_kernel.h"
+#include "tdec_internal.h"
 
 using namespace srsran_amd;
 
@@ -299,9 +300,6 @@ void qpp_coeffs(uint32_t idx, uint32_t* f1, uint32_t* f2)
   *f1 = kF1[idx];
   *f2 = kF2[idx];
 }
-}  // namespace srsran_amd
-
-namespace srsran_amd {
 
 int tdec_cb_index(uint32_t K) { return cb_index(K); }
 

@@ -15,10 +15,7 @@
 #include "dev_buf.h"
 #include "devkey.h"
 #include "enc_kernel.h"
-
-namespace srsran_amd {
-void qpp_coeffs(uint32_t idx, uint32_t* f1, uint32_t* f2);
-}
+#include "tdec_internal.h"
 
 namespace {
 using srsran_amd::RmTxLut;

@@ -1,5 +1,5 @@
 """PUSCH receive, host side and checker (no GPU): the library's DMRS generator (refsignal_ul.c:95-358
-restated in csrc/pusch_api.cpp) against the oracle built on the reference's compiled
+restated in csrc/refsignal_ul_api.cpp) against the oracle built on the reference's compiled
 srsran_zc_sequence_generate_lte / srsran_group_hopping_f_gh; the transform-precoding PRB rule
 against dft_precoding.c:88-112; and the checker chain itself: test transmitter -> oracle channel
 estimator -> equaliser / inverse DFT -> reference demapper / descrambler -> reference UCI + UL-SCH

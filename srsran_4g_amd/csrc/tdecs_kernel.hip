@@ -325,10 +325,6 @@ __device__ __forceinline__ uint32_t pin(uint32_t v)
   asm volatile("" : "+v"(v));
   return v;
 }
-[[maybe_unused]] __device__ __forceinline__ St pin(const St& p)  // used by the two-wave build only
-{
-  return St{u2v(pin(v2u(p.a))), u2v(pin(v2u(p.b))), u2v(pin(v2u(p.c))), u2v(pin(v2u(p.d)))};
-}
 
 // The LLR o of position k: S update (vec_sub, wraps) and, when the half-iteration's decision is
 // needed, its bit (turbodecoder.c:370-378: the sign of ext1 after DEC1, of app1 after DEC2).  Two bit layouts:
@@ -397,7 +393,7 @@ __device__ __forceinline__ uint32_t nat_byte(const uint32_t* bits, int L, int Ls
 
 // Phase-2 alpha side, window at t0 >= W: beta[t0+1 .. cc] recomputed from the stored beta at
 // cc = min(t0 + W, L) (checkpoint), then alpha + LLR of t0 .. cc-1.
-template <bool D2, int BITS, bool FULL, bool GCK = false>
+template <bool D2, int BITS, bool FULL>
 __device__ __forceinline__ St alpha_llr_window(const Lane& c, St P, int t0, St Pb, const uint32_t* xw,
                                                const uint32_t* aux)
 {
@@ -420,7 +416,7 @@ __device__ __forceinline__ St alpha_llr_window(const Lane& c, St P, int t0, St P
 #pragma unroll
   for (int i = 0; i < W; i++) {
     if (FULL || t0 + i < L) {
-      const Cand  cd = cand(P, bm(GCK ? pin(xw[i]) : xw[i]));
+      const Cand  cd = cand(P, bm(xw[i]));
       const short o  = llr(cd, bw[i]);
       P              = next<false>(cd);
       if ((i & 1) == 0) P = norm(P);  // t0 >= W: every even position
@@ -644,7 +640,7 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
       if (GCK) {
         ckn = ck_get<true>(c, min(ma + 1, Ma - 1));
       }
-      P = alpha_llr_window<D2, BITS, true, GCK>(c, P, ma * W, GCK ? ckc : ck_get<false>(c, ma), xw, aux);
+      P = alpha_llr_window<D2, BITS, true>(c, P, ma * W, GCK ? ckc : ck_get<false>(c, ma), xw, aux);
       pp.taken(c);
       if (GCK) {
         ckc = ckn;
@@ -652,7 +648,7 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
     }
     if (Ma > Mfull) {
       pp.template next<true>(c, 0, xw, aux);
-      alpha_llr_window<D2, BITS, false, GCK>(c, P, Mfull * W, GCK ? ckc : ck_get<false>(c, Mfull), xw, aux);
+      alpha_llr_window<D2, BITS, false>(c, P, Mfull * W, GCK ? ckc : ck_get<false>(c, Mfull), xw, aux);
     }
     TDECS_STAMP(st0 + 4);
   } else {
@@ -711,7 +707,7 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
     phase_barrier<GCK>();
     TDECS_STAMP(st0 + 3);
     // phase 2: windows [0, h) from the top: alpha recomputed from the entry checkpoint, then
-    // beta backwards with the LLR of every position
+    // beta backwards with the LLR of every position (GCK: beta backwards first, then alpha + LLR forwards)
     St ckc;  // GCK: the current window's checkpoint
     if (GCK) {
       ckc = ck_get<true>(c, h - 1);
@@ -724,28 +720,47 @@ __device__ __forceinline__ void map16s(const Lane& cin, int wave, int st0)
       if (GCK) {
         ckc = ck_get<true>(c, max(mb - 1, 0));
       }
-      St aw[W];  // alpha entering each position (candidates rebuilt at LLR time)
-#pragma unroll
-      for (int i = 0; i < W; i++) {
-        aw[i] = Pa;
-        if (i < W - 1) {
-          Pa = step<false>(Pa, xw[i]);
-          if (nrm(t0, i)) Pa = norm(Pa);
-        }
-      }
       uint32_t wbits = 0;
+      if constexpr (GCK) {
+        // the window's backward recursion first, the stored beta above each position kept (the 64 registers aw
+        // takes below); then forward from the checkpoint as alpha_llr_window: one candidate set a position for
+        // the LLR and the step, where rebuilding it at LLR time from kept alphas cost a third set
+        St bw[W];
 #pragma unroll
-      for (int i = W - 1; i >= 0; i--) {
-        short o;
-        if constexpr (GCK) {  // rebuilt here as written, not kept from the loop above (96 registers)
-          o = llr(cand(pin(aw[i]), bm(pin(xw[i]))), Bst);
-        } else {
-          o = llr(cand(aw[i], bm(xw[i])), Bst);
+        for (int i = W - 1; i >= 0; i--) {
+          bw[i] = Bst;
+          P     = step<true>(P, xw[i]);
+          Bst   = P;
+          if (nrm(t0, i)) P = norm(P);
         }
-        P             = step<true>(P, xw[i]);
-        Bst           = P;
-        if (nrm(t0, i)) P = norm(P);
-        wbits |= emit<D2, BITS>(c, t0 + i, o, aux[i], xw[i]) << i;
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+          const Cand  cd = cand(Pa, bm(xw[i]));
+          const short o  = llr(cd, bw[i]);
+          if (i < W - 1) {
+            Pa = next<false>(cd);
+            if (nrm(t0, i)) Pa = norm(Pa);
+          }
+          wbits |= emit<D2, BITS>(c, t0 + i, o, aux[i], xw[i]) << i;
+        }
+      } else {
+        St aw[W];  // alpha entering each position (the compiler keeps its candidates for the LLR below)
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+          aw[i] = Pa;
+          if (i < W - 1) {
+            Pa = step<false>(Pa, xw[i]);
+            if (nrm(t0, i)) Pa = norm(Pa);
+          }
+        }
+#pragma unroll
+        for (int i = W - 1; i >= 0; i--) {
+          const short o = llr(cand(aw[i], bm(xw[i])), Bst);
+          P             = step<true>(P, xw[i]);
+          Bst           = P;
+          if (nrm(t0, i)) P = norm(P);
+          wbits |= emit<D2, BITS>(c, t0 + i, o, aux[i], xw[i]) << i;
+        }
       }
       if (BITS == 2 && !D2) {
         flush_bits(c, t0, wbits);

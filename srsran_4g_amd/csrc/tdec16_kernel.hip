@@ -753,81 +753,6 @@ __global__ __launch_bounds__(128, 2) void tdec16_multi_kernel(const TdecArgs* __
   tdec16_body<false>(a, (int)(b - first[lo]));
 }
 
-// Which 16-sub-block decoder a launch of n blocks gets (K = 6144, 8 half-iterations, ms per launch,
-// gpurun_out r03d -> profiles/r03_tdec_kernels.jsonl):
-//      n      quad (tdec_kernel<16>)   lane pair (tdec16_kernel)   single lane (tdec16s_kernel)
-//    256            0.258                    0.275                        0.344
-//    512            0.339                    0.282                        0.348
-//   1024            0.403                    0.394                        0.362
-//   2048            0.766                    0.457                        0.382
-// The quad decoder (one block a workgroup) fills the chip best below ~512 blocks, the lane pair between,
-// and the single-lane decoder (64 lanes a wave on 4 blocks, the densest mapping) from 1024 on.
-// srsran_tdec_gpu_set_pair_threshold() / _single_threshold() move the thresholds (tests force each
-// kernel onto small batches with 0).
-static uint32_t g_pair_min_cb = 512u;
-void     tdec16_set_min_cb(uint32_t n) { __atomic_store_n(&g_pair_min_cb, n, __ATOMIC_RELAXED); }
-uint32_t tdec16_min_cb() { return __atomic_load_n(&g_pair_min_cb, __ATOMIC_RELAXED); }
-bool     tdec16_pays(uint32_t ncb) { return ncb >= tdec16_min_cb(); }
-// srsran_tdec_gpu_set_single_threshold(): blocks a launch from which the single-lane decoders
-// (tdecs_kernel.hip, 16-sub-block class) replaces the lane pair.  Between 512 and 1024 blocks
-// (K = 6144, gpurun_out r03af): single lane / lane pair 0.345 / 0.385 ms at 640, 0.349 / 0.390 at 768,
-// 0.359 / 0.394 at 896, 0.361 / 0.397 at 1014 (the PUSCH batch of 78 UEs x 13 blocks: 0.108 vs 0.113 ms
-// with early stop); the lane pair is ahead at 512 (0.282 vs 0.348): from 576 blocks.
-static uint32_t g_single_min_cb = 576u;
-void     tdec16s_set_min_cb(uint32_t n) { __atomic_store_n(&g_single_min_cb, n, __ATOMIC_RELAXED); }
-uint32_t tdec16s_min_cb() { return __atomic_load_n(&g_single_min_cb, __ATOMIC_RELAXED); }
-// The 8-sub-block class: its quad decoder (one block a workgroup) stays ahead up to ~1024 blocks a launch
-// (K = 512: 0.060 vs 0.085 ms at 512, 0.081 vs 0.086 ms at 1024) and the single-lane decoder is ahead on
-// the fused class launch (32 sizes x 256 = 8192 blocks: 0.30 vs 0.53 ms): from 4096 blocks by default.
-static uint32_t g_single8_min_cb = 4096u;
-// srsran_tdec_gpu_set_w8_max_k(): single-lane launches whose block sizes are all <= this K use the build
-// with 8-step windows (tdecs_kernel.hip, TDECS_W = 8: 164-191 VGPRs, two waves a SIMD where LDS allows).
-// Default 800 = the whole 8-sub-block class (408 <= K <= 800), where it wins: the fused class launch of
-// 32 sizes x 1024 blocks 0.71 vs 0.91 ms, x 4096 blocks 2.30 vs 3.39 ms (gpurun_out r03l).  The 16-sub-block
-// class keeps 16-step windows: its 8-step build is slower at every K measured (2048 blocks, K = 1024 / 2048
-// / 4096 / 6144: 0.129 / 0.219 / 0.395 / 0.738 ms against 0.096 / 0.153 / 0.268 / 0.380 ms): twice the
-// windows a sub-block for the same training overlap, and at 19 KB of LDS a block the second wave a
-// SIMD does not fit at large K anyway.
-static uint32_t g_w8_max_k = 800u;
-// srsran_tdec_gpu_set_w8_fused_max_k(): in a fused multi-size launch of the 16-sub-block single-lane class,
-// the sizes up to this K form their own launch on the 8-step-window build (their workgroups, at 164-191
-// registers and little LDS, share SIMDs with the large sizes' workgroups).  All-188 step, one box,
-// alternating runs (gpurun_out r03z): cut at 800 (none) 12.22 ms, 1536 11.65 ms, 2368 11.71-11.73 ms,
-// 3136 12.37 ms.  With the 16-step part cut again at SRSRAN_AMD_TDEC_MIDCUT = 3072 (r06v, one box, alternating):
-// 1024 10.95 ms, 1536 10.615 / 10.621 ms, 1792 10.68 ms, 2048 10.686 / 10.71 ms, 2560 11.34 ms.
-static uint32_t g_w8_fused_max_k = 1536u;
-void     tdecs_set_w8_fused_max_k(uint32_t k) { __atomic_store_n(&g_w8_fused_max_k, k, __ATOMIC_RELAXED); }
-uint32_t tdecs_w8_fused_max_k() { return __atomic_load_n(&g_w8_fused_max_k, __ATOMIC_RELAXED); }
-void     tdecs_set_w8_max_k(uint32_t k) { __atomic_store_n(&g_w8_max_k, k, __ATOMIC_RELAXED); }
-uint32_t tdecs_w8_max_k() { return __atomic_load_n(&g_w8_max_k, __ATOMIC_RELAXED); }
-void     tdec8s_set_min_cb(uint32_t n) { __atomic_store_n(&g_single8_min_cb, n, __ATOMIC_RELAXED); }
-uint32_t tdec8s_min_cb() { return __atomic_load_n(&g_single8_min_cb, __ATOMIC_RELAXED); }
-// srsran_tdec_gpu_set_generic_single_threshold(): the generic class (K <= 400) keeps tdec_kernel.hip's
-// quad decoder by default: one lane per block and direction runs the whole K-step recursion serially, and
-// at 1024 blocks per size (47104 blocks) tdec1s_kernel takes 1.47 ms against the quad decoder's 0.78 ms
-// (profiles/r03_tdec_kernels.jsonl), so tdec1s is selected only when a caller lowers this threshold.
-static uint32_t g_single1_min_cb = 0xffffffffu;
-void     tdec1s_set_min_cb(uint32_t n) { __atomic_store_n(&g_single1_min_cb, n, __ATOMIC_RELAXED); }
-uint32_t tdec1s_min_cb() { return __atomic_load_n(&g_single1_min_cb, __ATOMIC_RELAXED); }
-int      tdec16_choice(uint32_t ncb) { return ncb >= tdec16s_min_cb() ? 2 : tdec16_pays(ncb) ? 1 : 0; }
-
-bool tdec16_eligible(int nsb, const TdecArgs& a)
-{
-  return nsb == 16 && a.layout_sb && a.n_start == 0 && a.state == nullptr && a.L >= (uint32_t)OVL &&
-         tdec16_choice(a.ncb) > 0;
-}
-
-bool tdec8s_eligible(int nsb, const TdecArgs& a)
-{
-  return nsb == 8 && a.layout_sb && a.n_start == 0 && a.state == nullptr && a.L >= (uint32_t)OVL &&
-         a.ncb >= tdec8s_min_cb();
-}
-
-bool tdec1s_eligible(int nsb, const TdecArgs& a)
-{
-  return nsb == 1 && a.n_start == 0 && a.state == nullptr && a.ncb >= tdec1s_min_cb();
-}
-
 size_t tdec16_lds_bytes(const TdecArgs& a)
 {
   const Geo16 g = geo16((int)a.K, (int)a.Ls, (int)((a.L + W - 1) / W));

@@ -24,7 +24,7 @@
 #include "stage_copy.h"
 #include "dev_buf.h"
 #include "devkey.h"
-#include "tdec_kernel.h"
+#include "tdec_dispatch.h"
 #include "tdec8bit_kernel.h"
 #include "tdec_internal.h"
 
@@ -170,17 +170,11 @@ Config* get_config(uint32_t K, int nsb)
   return c;
 }
 
-int auto_nsb(uint32_t K)
-{
-  const uint32_t n = srsran_tdec_autoimp_get_subblocks(K);
-  return n ? (int)n : 1;
-}
-
 int nsb_for(const srsran_tdec_t* h, uint32_t K)
 {
   switch (h->dec_type) {
     case SRSRAN_TDEC_AUTO:
-      return auto_nsb(K);
+      return tdec_auto_nsb(K);
     case SRSRAN_TDEC_GENERIC:
       return 1;
     case SRSRAN_TDEC_SSE_WINDOW:
@@ -205,8 +199,9 @@ struct Ctx {
 
 const size_t kMaxIn = 3 * (SRSRAN_TCOD_MAX_LEN_CB + 32) + SRSRAN_TCOD_TOTALTAIL;
 
-int enqueue(const Config* c, const short* d_in, uint32_t in_stride, int layout_sb, uint8_t* d_out, uint32_t ncb,
-            int n_start, int n_end, short* d_state, hipStream_t stream)
+// The arguments of a plain launch of ncb blocks of c's size: its geometry plus the pointer and iteration fields.
+TdecArgs make_args(const Config* c, const short* d_in, uint32_t in_stride, int layout_sb, uint8_t* d_out, uint32_t ncb,
+                   int n_start, int n_end, short* d_state)
 {
   TdecArgs a  = c->proto;
   a.in        = d_in;
@@ -221,7 +216,14 @@ int enqueue(const Config* c, const short* d_in, uint32_t in_stride, int layout_s
   a.tfwd_nat  = c->d_tfwd_nat;
   a.trev_nat  = c->d_trev_nat;
   a.state     = d_state;
-  hipError_t e = tdec_launch(c->nsb, a, stream);
+  return a;
+}
+
+int enqueue(const Config* c, const short* d_in, uint32_t in_stride, int layout_sb, uint8_t* d_out, uint32_t ncb,
+            int n_start, int n_end, short* d_state, hipStream_t stream)
+{
+  const TdecArgs a = make_args(c, d_in, in_stride, layout_sb, d_out, ncb, n_start, n_end, d_state);
+  hipError_t     e = tdec_launch(c->nsb, a, stream);
   if (e != hipSuccess) {
     fprintf(stderr, "[srsran_tdec] launch failed: %s\n", hipGetErrorString(e));
     return SRSRAN_ERROR;
@@ -316,24 +318,13 @@ int tdec_sch_enqueue(uint32_t      K,
   if (ncb == 0) {
     return SRSRAN_SUCCESS;
   }
-  Config* c = get_config(K, auto_nsb(K));
+  Config* c = get_config(K, tdec_auto_nsb(K));
   const XpowTables* xp = xpow_tables();
   if (!c || !xp) {
     return SRSRAN_ERROR;
   }
-  TdecArgs a   = c->proto;
-  a.in         = nullptr;
-  a.in_stride  = 0;
-  a.layout_sb  = c->nsb > 1 ? 1 : 0;  // soft buffer layout (rm_turbo.c:403-418)
-  a.ncb        = ncb;
-  a.n_start    = 0;
-  a.n_end      = n_end > 0 ? n_end : 1;
-  a.out        = d_out;
-  a.tfwd       = c->d_tfwd;
-  a.trev       = c->d_trev;
-  a.tfwd_nat   = c->d_tfwd_nat;
-  a.trev_nat   = c->d_trev_nat;
-  a.state      = nullptr;
+  // soft buffer layout (rm_turbo.c:403-418); the blocks' inputs come from d_cbs
+  TdecArgs a   = make_args(c, nullptr, 0, 1, d_out, ncb, 0, n_end > 0 ? n_end : 1, nullptr);
   a.cbs        = d_cbs;
   a.out_stride = out_stride;
   a.noi_out    = d_noi;
@@ -434,13 +425,8 @@ extern "C" {
 
 uint32_t srsran_tdec_autoimp_get_subblocks(uint32_t long_cb)
 {
-  if (!(long_cb % 16) && long_cb > 800) {
-    return 16;
-  }
-  if (!(long_cb % 8) && long_cb > 400) {
-    return 8;
-  }
-  return 0;
+  const int nsb = tdec_auto_nsb(long_cb);
+  return nsb > 1 ? (uint32_t)nsb : 0;
 }
 
 uint32_t srsran_tdec_autoimp_get_subblocks_8bit(uint32_t long_cb)
@@ -465,7 +451,7 @@ int srsran_tdec_gpu_available(void)
 
 const char* srsran_tdec_gpu_kernel_name(uint32_t long_cb)
 {
-  switch (auto_nsb(long_cb)) {
+  switch (tdec_auto_nsb(long_cb)) {
     case 16:
       return "tdec_kernel<16>";
     case 8:
@@ -477,64 +463,52 @@ const char* srsran_tdec_gpu_kernel_name(uint32_t long_cb)
 
 const char* srsran_tdec_gpu_last_kernel(void) { return tdec_last_kernel(); }
 
-void srsran_tdec_gpu_set_pair_threshold(uint32_t nof_cb) { tdec16_set_min_cb(nof_cb); }
+void srsran_tdec_gpu_set_pair_threshold(uint32_t nof_cb) { tdec_tune(&TdecTuning::pair_min_cb, nof_cb); }
 
-uint32_t srsran_tdec_gpu_get_pair_threshold(void) { return tdec16_min_cb(); }
+uint32_t srsran_tdec_gpu_get_pair_threshold(void) { return tdec_tuning().pair_min_cb; }
 
-void srsran_tdec_gpu_set_w8_max_k(uint32_t k) { tdecs_set_w8_max_k(k); }
+void srsran_tdec_gpu_set_w8_max_k(uint32_t k) { tdec_tune(&TdecTuning::w8_max_k, k); }
 
-uint32_t srsran_tdec_gpu_get_w8_max_k(void) { return tdecs_w8_max_k(); }
+uint32_t srsran_tdec_gpu_get_w8_max_k(void) { return tdec_tuning().w8_max_k; }
 
-void srsran_tdec_gpu_set_w8_fused_max_k(uint32_t k) { tdecs_set_w8_fused_max_k(k); }
+void srsran_tdec_gpu_set_w8_fused_max_k(uint32_t k) { tdec_tune(&TdecTuning::w8_fused_max_k, k); }
 
-uint32_t srsran_tdec_gpu_get_w8_fused_max_k(void) { return tdecs_w8_fused_max_k(); }
-
-
+uint32_t srsran_tdec_gpu_get_w8_fused_max_k(void) { return tdec_tuning().w8_fused_max_k; }
 
 void srsran_tdec_gpu_set_class_single_threshold(uint32_t nof_subblocks, uint32_t nof_cb)
 {
   if (nof_subblocks == 16) {
-    tdec16s_set_min_cb(nof_cb);
+    tdec_tune(&TdecTuning::single16_min_cb, nof_cb);
   } else if (nof_subblocks == 8) {
-    tdec8s_set_min_cb(nof_cb);
+    tdec_tune(&TdecTuning::single8_min_cb, nof_cb);
   } else if (nof_subblocks <= 1) {
-    tdec1s_set_min_cb(nof_cb);
+    tdec_tune(&TdecTuning::single1_min_cb, nof_cb);
   }
 }
 
 uint32_t srsran_tdec_gpu_get_class_single_threshold(uint32_t nof_subblocks)
 {
-  return nof_subblocks == 16 ? tdec16s_min_cb() : nof_subblocks == 8 ? tdec8s_min_cb() : tdec1s_min_cb();
+  const TdecTuning t = tdec_tuning();
+  return nof_subblocks == 16 ? t.single16_min_cb : nof_subblocks == 8 ? t.single8_min_cb : t.single1_min_cb;
 }
 
 void srsran_tdec_gpu_set_single_threshold(uint32_t nof_cb)
 {
-  tdec16s_set_min_cb(nof_cb);
-  tdec8s_set_min_cb(nof_cb);
+  tdec_tune(&TdecTuning::single16_min_cb, nof_cb);
+  tdec_tune(&TdecTuning::single8_min_cb, nof_cb);
 }
 
-uint32_t srsran_tdec_gpu_get_single_threshold(void) { return tdec16s_min_cb(); }
+uint32_t srsran_tdec_gpu_get_single_threshold(void) { return tdec_tuning().single16_min_cb; }
 
-void srsran_tdec_gpu_set_generic_single_threshold(uint32_t nof_cb) { tdec1s_set_min_cb(nof_cb); }
+void srsran_tdec_gpu_set_generic_single_threshold(uint32_t nof_cb) { tdec_tune(&TdecTuning::single1_min_cb, nof_cb); }
 
-uint32_t srsran_tdec_gpu_get_generic_single_threshold(void) { return tdec1s_min_cb(); }
+uint32_t srsran_tdec_gpu_get_generic_single_threshold(void) { return tdec_tuning().single1_min_cb; }
 
+// the kernel of a plain launch of nof_cb blocks on the SB layout
 const char* srsran_tdec_gpu_kernel_name_batch(uint32_t long_cb, uint32_t nof_cb)
 {
-  const int nsb = auto_nsb(long_cb);
-  if (nsb == 16) {
-    const int k = tdec16_choice(nof_cb);
-    if (k) {
-      return k == 2 ? "tdec16s_kernel" : "tdec16_kernel";
-    }
-  }
-  if (nsb == 8 && nof_cb >= tdec8s_min_cb()) {
-    return "tdec8s_kernel";
-  }
-  if (nsb == 1 && nof_cb >= tdec1s_min_cb()) {
-    return "tdec1s_kernel";
-  }
-  return srsran_tdec_gpu_kernel_name(long_cb);
+  const int nsb = tdec_auto_nsb(long_cb);
+  return tdec_build(tdec_pick_build(tdec_tuning(), nsb, long_cb, nof_cb, true, false, false)).api_name;
 }
 
 int srsran_tdec_init(srsran_tdec_t* h, uint32_t max_long_cb)
@@ -724,7 +698,7 @@ int srsran_tdec_gpu_run_batch(uint32_t       long_cb,
   if (!d_input || !d_output || cb_index(long_cb) < 0) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  Config* c = get_config(long_cb, auto_nsb(long_cb));
+  Config* c = get_config(long_cb, tdec_auto_nsb(long_cb));
   if (!c) {
     return SRSRAN_ERROR;
   }
@@ -739,7 +713,7 @@ int srsran_tdec_gpu_run_batch(uint32_t       long_cb,
 namespace {
 // Internal fork/join stream pool for srsran_tdec_gpu_run_multi (per device).
 constexpr int kPoolStreams = 4;
-// Device descriptors of one fused multi-size launch (per decoder class).
+// Device descriptors of one fused multi-size launch (per staging slot of the plan).
 struct MultiDesc {
   PinBuf<char> h_stage;          // pinned: TdecArgs[n] | ck_off[n] (uint64) | first[n]
   DevBuf<char> d_stage;          // same capacity
@@ -752,29 +726,15 @@ struct StreamPool {
   hipStream_t s[kPoolStreams];
   hipEvent_t  done[kPoolStreams];
   hipEvent_t  fork;
-  hipEvent_t  large_done;  // the 16-step part's largest sizes finished (gates the other classes, tdec_gate())
-  // launch entries: 16 (16-step, top residency tier), 16 (16-step, the other large K), 16 (16-step, mid K),
-  // 16 (8-step part), 8, generic x 2
-  MultiDesc   md[7];
+  hipEvent_t  large_done;  // the 16-step part's largest sizes finished (gates the other classes)
+  MultiDesc   md[kTdecPlanSlots];
   // window checkpoints of the fused 16-step launches (tdecs_ck_geo.h): grow-only, one region a workgroup, every
-  // launch of a call its own part of it; the launches that use it all run on s[0] (or, serial mode, on s[0] too)
+  // launch of a call its own part of it; the launches that use it all run on s[0]
   DevBuf<uint8_t>       d_ck;
   std::map<size_t, int> wg_per_cu;  // the fused 16-step kernel's workgroups a CU by LDS bytes a workgroup (queried once)
 };
 std::mutex               g_pool_mu;
 std::vector<StreamPool*> g_pools;
-
-// How the classes of a fused multi-size call share the device (SRSRAN_AMD_TDEC_MULTI, read once):
-// 0 "streams": one pool stream a class, equal priority; 1 "priority": the first (longest) class's stream at the
-// device's highest priority, the others at the lowest; 2 "serial": every class on one stream, longest first.
-int multi_mode()
-{
-  static const int m = [] {
-    const char* e = getenv("SRSRAN_AMD_TDEC_MULTI");
-    return !e ? 0 : !strcmp(e, "priority") ? 1 : !strcmp(e, "serial") ? 2 : 0;
-  }();
-  return m;
-}
 
 StreamPool* get_pool()
 {
@@ -790,12 +750,8 @@ StreamPool* get_pool()
   }
   StreamPool* p = new StreamPool();
   p->device     = dev;
-  int lo = 0, hi = 0;
-  if (multi_mode() == 1 && hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) {
-    lo = hi = 0;
-  }
   for (int i = 0; i < kPoolStreams; i++) {
-    if (hipStreamCreateWithPriority(&p->s[i], hipStreamNonBlocking, i == 0 ? hi : lo) != hipSuccess ||
+    if (hipStreamCreateWithPriority(&p->s[i], hipStreamNonBlocking, 0) != hipSuccess ||
         srsran_amd::ring_event_create(&p->done[i]) != hipSuccess) {
       return nullptr;
     }
@@ -812,43 +768,6 @@ StreamPool* get_pool()
   return p;
 }
 
-// The generic class's quad launch sizes its LDS for its largest K (about 45 KB a workgroup at K = 400: three a
-// CU); its sizes up to this K run as a second launch with LDS for them, more workgroups a CU
-// (SRSRAN_AMD_TDEC_GEN_CUT, read once; 0 = one launch).
-uint32_t gen_cut()
-{
-  static const uint32_t c = [] {
-    const char* e = getenv("SRSRAN_AMD_TDEC_GEN_CUT");
-    return e ? (uint32_t)atoi(e) : 0u;
-  }();
-  return c;
-}
-
-// The 16-step part of a fused 16-sub-block class is cut once more at this K (SRSRAN_AMD_TDEC_MIDCUT, read once;
-// 0 = no mid part): its sizes above run first, cut by residency (srsran_tdec_gpu_run_multi: three or four workgroups
-// a CU at two waves a SIMD, nothing else fits beside them), its sizes up to the cut follow on the same stream with
-// their own, smaller LDS figure -- room beside them for the 8-step part's, the 8-sub-block class's and the generic
-// class's workgroups.  2048 from the sweep with the two-wave kernel (HISTORY.md; 3072 at one wave a SIMD).
-uint32_t tdec_midcut()
-{
-  static const uint32_t c = [] {
-    const char* e = getenv("SRSRAN_AMD_TDEC_MIDCUT");
-    return e ? (uint32_t)atoi(e) : 2048u;
-  }();
-  return c;
-}
-// With a mid cut, the other classes' launches wait for the large sizes to finish (SRSRAN_AMD_TDEC_GATE, read once;
-// default on): started at once they only take CUs the large workgroups would have used, since no large workgroup
-// leaves room beside it.
-bool tdec_gate()
-{
-  static const bool g = [] {
-    const char* e = getenv("SRSRAN_AMD_TDEC_GATE");
-    return e ? atoi(e) != 0 : true;
-  }();
-  return g;
-}
-
 // Workgroups of the fused 16-step kernel that a CU holds at `lds` bytes each (0: the query failed).
 int fused16_wg_per_cu(StreamPool* p, size_t lds)
 {
@@ -858,17 +777,10 @@ int fused16_wg_per_cu(StreamPool* p, size_t lds)
   }
   return it->second;
 }
-
-// Rough serial-latency model used only to order launches (longest first).
-double launch_cost(uint32_t K, uint32_t ncb)
-{
-  const int    nsb   = auto_nsb(K);
-  const double chain = nsb > 1 ? 3.0 * (K / nsb) + 160.0 : 3.0 * (K + 3);
-  const double waves = (double)ncb * 4 * nsb / 64.0;
-  return chain * (1.0 + waves / 1024.0);
-}
 }  // namespace
 
+// Issues the launches that tdec_multi_plan (tdec_plan.h) lays out, between a fork of the pool streams from the
+// caller's stream and a join back into it.
 int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
                               const uint32_t*       long_cb,
                               const int16_t* const* d_input,
@@ -885,13 +797,14 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
   if (!long_cb || !d_input || !in_stride || !d_output || !nof_cb) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  std::vector<Config*>  cfg(nof_groups);
-  std::vector<uint32_t> order(nof_groups);
+  const int              n_end = nof_iterations > 0 ? (int)nof_iterations : 1;
+  std::vector<Config*>   cfg(nof_groups);
+  std::vector<TdecGroup> groups(nof_groups);
   for (uint32_t g = 0; g < nof_groups; g++) {
     if (cb_index(long_cb[g]) < 0 || !d_input[g] || !d_output[g]) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
-    cfg[g] = get_config(long_cb[g], auto_nsb(long_cb[g]));
+    cfg[g] = get_config(long_cb[g], tdec_auto_nsb(long_cb[g]));
     if (!cfg[g]) {
       return SRSRAN_ERROR;
     }
@@ -899,15 +812,20 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
     if (in_stride[g] < len) {
       return SRSRAN_ERROR_INVALID_INPUTS;
     }
-    order[g] = g;
+    groups[g] = {long_cb[g], nof_cb[g]};
   }
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    return launch_cost(long_cb[a], nof_cb[a]) > launch_cost(long_cb[b], nof_cb[b]);
-  });
   StreamPool* p = get_pool();
   if (!p) {
     return SRSRAN_ERROR;
   }
+  auto args = [&](uint32_t g) {
+    return make_args(cfg[g], d_input[g], in_stride[g], layout_sb, d_output[g], nof_cb[g], 0, n_end, nullptr);
+  };
+  auto residency = [&](uint32_t K) {  // of one of the groups' sizes
+    const Config* c = cfg[std::find(long_cb, long_cb + nof_groups, K) - long_cb];
+    return fused16_wg_per_cu(p, tdecs16::multi_lds_bytes(c->proto));
+  };
+  const TdecMultiPlan plan = tdec_multi_plan(groups.data(), nof_groups, layout_sb != 0, tdec_tuning(), residency);
   hipStream_t user = (hipStream_t)stream;
   if (hipEventRecord(p->fork, user) != hipSuccess) {
     return SRSRAN_ERROR;
@@ -915,35 +833,11 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
   for (int i = 0; i < kPoolStreams; i++) {
     hipStreamWaitEvent(p->s[i], p->fork, 0);
   }
-  const int n_end = nof_iterations > 0 ? (int)nof_iterations : 1;
-  int       ret   = SRSRAN_SUCCESS;
-  // One fused launch per decoder class (16 / 8 / generic): the sizes of a class share one grid
-  // (more workgroups in flight than per-size launches, no per-launch tail); classes run on
-  // separate pool streams, longest first.  A single-lane 16-sub-block class is cut in two at
-  // tdecs_w8_fused_max_k(): its sizes up to there run the 8-step-window build (fewer registers and
-  // little LDS a workgroup: their workgroups can share SIMDs with the large sizes' ones) as their own
-  // launch.
-  // The fused 16-step kernel runs two waves a SIMD and keeps its checkpoints out of LDS, so the workgroups a CU holds
-  // depend on the launch's LDS figure: the sizes above the mid cut are cut once more where that residency changes
-  // (three a CU at K = 6144, four -- the register limit -- from about K = 4600 down), each part with the LDS of
-  // its own largest K.
-  // launch entries: 16 (16-step, K > mid cut, the residency of the largest K), 16 (16-step, K > mid cut, the rest),
-  // 16 (16-step, cut < K <= mid cut), 16 (8-step part), 8, generic x 2
-  const int      cls_nsb[7] = {16, 16, 16, 16, 8, 1, 1};
-  const int      cls_st[7]  = {0, 0, 0, 1, 2, 3, 3};  // pool stream of each entry (the 16-step parts: one stream)
-  const uint32_t midcut     = tdec_midcut();
-  const uint32_t cut        = std::max(tdecs_w8_max_k(), tdecs_w8_fused_max_k());
-  bool           gated      = false;
-  bool           mid_run    = false;  // entry 2 launched: the 16-step part was cut at midcut
   // the checkpoint scratch of this call's fused 16-step launches, allocated before the first of them
   uint64_t ck_need = 0, ck_used = 0;
-  const Config* top16 = nullptr;  // the largest 16-step size
-  for (uint32_t g = 0; g < nof_groups && layout_sb; g++) {
-    if (cfg[g]->nsb == 16 && cfg[g]->proto.K > cut && nof_cb[g] > 0) {
-      TdecArgs a = cfg[g]->proto;
-      a.ncb      = nof_cb[g];
-      ck_need += tdecs16::multi_ck_bytes(a);
-      top16 = top16 && top16->proto.K > a.K ? top16 : cfg[g];
+  for (const TdecMultiLaunch& l : plan.launches) {
+    for (size_t k = 0; l.scratch && k < l.groups.size(); k++) {
+      ck_need += tdecs16::multi_ck_bytes(args(l.groups[k]));
     }
   }
   if (ck_need > p->d_ck.cap()) {
@@ -952,79 +846,31 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
       return SRSRAN_ERROR;
     }
   }
-  auto residency = [&](const Config* c) { return fused16_wg_per_cu(p, tdecs16::multi_lds_bytes(c->proto)); };
-  const int top_res = top16 ? residency(top16) : 0;
-  for (int ci = 0; ci < 7 && ret == SRSRAN_SUCCESS; ci++) {
-    if (ci == 2 && hipEventRecord(p->large_done, p->s[0]) != hipSuccess) {  // behind the large sizes (entries 0, 1)
+  int ret = SRSRAN_SUCCESS;
+  for (size_t li = 0; li < plan.launches.size() && ret == SRSRAN_SUCCESS; li++) {
+    const TdecMultiLaunch& l  = plan.launches[li];
+    hipStream_t            st = p->s[l.stream];
+    if (li == plan.large_done_at && hipEventRecord(p->large_done, p->s[0]) != hipSuccess) {
       ret = SRSRAN_ERROR;
       break;
     }
-    // with the 16-step part cut at midcut, the other classes start when its large sizes are done, beside the mid part
-    gated = ci >= 3 && mid_run && tdec_gate() && multi_mode() != 2;
-    std::vector<uint32_t> gs;
-    uint32_t              cls_cb = 0;  // blocks of the whole class (decides the kernel)
-    for (uint32_t i = 0; i < nof_groups; i++) {
-      if (cfg[order[i]]->nsb == cls_nsb[ci] && nof_cb[order[i]] > 0) {
-        gs.push_back(order[i]);
-        cls_cb += nof_cb[order[i]];
-      }
-    }
-    if (gs.empty()) {
-      continue;
-    }
-    // 2 single lane (tdecs_kernel.hip), 1 lane pair (16 sub-blocks only), 0 quad
-    const int kind = cls_nsb[ci] == 1               ? (cls_cb >= tdec1s_min_cb() ? 2 : 0)   // natural layout
-                     : !layout_sb                   ? 0
-                     : cls_nsb[ci] == 16            ? tdec16_choice(cls_cb)
-                                                    : (cls_cb >= tdec8s_min_cb() ? 2 : 0);
-    if (cls_nsb[ci] == 16 && kind == 2) {
-      // entries 0, 1: K above the mid cut, by residency; entry 2: up to the mid cut; entry 3: up to the cut
-      const uint32_t lo = ci <= 1 ? std::max(cut, midcut) : ci == 2 ? cut : 0;
-      const uint32_t hi = ci <= 1 ? UINT32_MAX : ci == 2 ? std::max(cut, midcut) : cut;
-      gs.erase(std::remove_if(gs.begin(), gs.end(),
-                              [&](uint32_t g) {
-                                const uint32_t K = cfg[g]->proto.K;
-                                return !(K > lo && K <= hi) || (ci <= 1 && (residency(cfg[g]) == top_res) != (ci == 0));
-                              }),
-               gs.end());
-    } else if (ci >= 1 && ci <= 3) {
-      gs.clear();  // no second large part / 16-step mid part / 8-step part outside the single-lane class
-    } else if (ci >= 5 && kind == 0 && gen_cut() > 0) {  // generic quad: K above the cut, then the rest
-      const bool small = ci == 6;
-      gs.erase(std::remove_if(gs.begin(), gs.end(), [&](uint32_t g) { return (cfg[g]->proto.K <= gen_cut()) != small; }),
-               gs.end());
-    } else if (ci == 6) {
-      gs.clear();  // one generic launch
-    }
-    if (gs.empty()) {
-      continue;
-    }
-    mid_run        = mid_run || ci == 2;
-    hipStream_t st = p->s[multi_mode() == 2 ? 0 : cls_st[ci]];
-    if (gated && st != p->s[0] && hipStreamWaitEvent(st, p->large_done, 0) != hipSuccess) {
+    // with a mid part, the other classes start when the large sizes are done, beside it
+    if (l.gated && hipStreamWaitEvent(st, p->large_done, 0) != hipSuccess) {
       ret = SRSRAN_ERROR;
       break;
     }
-    if (gs.size() == 1) {
-      const uint32_t g = gs[0];
+    if (!l.fused) {
+      const uint32_t g = l.groups[0];
       ret = enqueue(cfg[g], d_input[g], in_stride[g], layout_sb, d_output[g], nof_cb[g], 0, n_end, nullptr, st);
       continue;
     }
-    const int  nsbc = cls_nsb[ci];
-    uint32_t   kmax = 0;
-    for (uint32_t g : gs) {
-      kmax = std::max(kmax, cfg[g]->proto.K);
-    }
-    const bool w8  = kind == 2 && nsbc > 1 && kmax <= (nsbc == 16 ? cut : tdecs_w8_max_k());  // 8-step windows
-    const bool gck = kind == 2 && nsbc == 16 && !w8;  // the fused 16-step kernel: checkpoints in p->d_ck
-    const int  cpw  = kind == 2   ? (nsbc == 16 ? tdecs16::cpw() : nsbc == 8 ? tdecs8::cpw() : tdecs1::cpw())
-                      : kind == 1 ? tdec16_cpw()
-                                  : tdec_cpw(nsbc);
-    const size_t   n     = gs.size();
-    const size_t   abyte = n * sizeof(TdecArgs);
-    const size_t   kbyte = n * sizeof(uint64_t);
-    const size_t   need  = abyte + kbyte + n * sizeof(uint32_t);
-    MultiDesc&     m     = p->md[ci];
+    const TdecBuildRow& row   = tdec_build(l.build);
+    const int           cpw   = row.cpw();
+    const size_t        n     = l.groups.size();
+    const size_t        abyte = n * sizeof(TdecArgs);
+    const size_t        kbyte = n * sizeof(uint64_t);
+    const size_t        need  = abyte + kbyte + n * sizeof(uint32_t);
+    MultiDesc&          m     = p->md[l.slot];
     if (m.used) {
       hipEventSynchronize(m.copied);
     }
@@ -1034,39 +880,20 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
         return SRSRAN_ERROR;
       }
     }
-    TdecArgs* ha    = reinterpret_cast<TdecArgs*>(m.h_stage.get());
-    uint64_t* hk    = reinterpret_cast<uint64_t*>(m.h_stage + abyte);  // bytes to each group's part of p->d_ck
-    uint32_t* hf    = reinterpret_cast<uint32_t*>(m.h_stage + abyte + kbyte);
-    uint32_t  nblk  = 0;
-    size_t    lds   = 0;
+    TdecArgs* ha   = reinterpret_cast<TdecArgs*>(m.h_stage.get());
+    uint64_t* hk   = reinterpret_cast<uint64_t*>(m.h_stage + abyte);  // bytes to each group's part of p->d_ck
+    uint32_t* hf   = reinterpret_cast<uint32_t*>(m.h_stage + abyte + kbyte);
+    uint32_t  nblk = 0;
+    size_t    lds  = 0;
     for (size_t k = 0; k < n; k++) {
-      const uint32_t g = gs[k];
-      const Config*  c = cfg[g];
-      TdecArgs       a = c->proto;
-      a.in             = d_input[g];
-      a.in_stride      = in_stride[g];
-      a.layout_sb      = c->nsb > 1 ? layout_sb : 0;
-      a.ncb            = nof_cb[g];
-      a.n_start        = 0;
-      a.n_end          = n_end;
-      a.out            = d_output[g];
-      a.tfwd           = c->d_tfwd;
-      a.trev           = c->d_trev;
-      a.tfwd_nat       = c->d_tfwd_nat;
-      a.trev_nat       = c->d_trev_nat;
-      a.state          = nullptr;
+      ha[k] = args(l.groups[k]);
       hk[k] = ck_used;
-      if (gck) {
-        ck_used += tdecs16::multi_ck_bytes(a);
+      hf[k] = nblk;
+      nblk += (ha[k].ncb + cpw - 1) / cpw;
+      if (l.scratch) {
+        ck_used += tdecs16::multi_ck_bytes(ha[k]);
       }
-      ha[k]            = a;
-      hf[k]            = nblk;
-      nblk += (nof_cb[g] + cpw - 1) / cpw;
-      lds = std::max(lds, kind == 2   ? (nsbc == 16  ? (w8 ? tdecs16w8::lds_bytes(a) : tdecs16::multi_lds_bytes(a))
-                                         : nsbc == 8 ? (w8 ? tdecs8w8::lds_bytes(a) : tdecs8::lds_bytes(a))
-                                                     : tdecs1::lds_bytes(a))
-                          : kind == 1 ? tdec16_lds_bytes(a)
-                                      : tdec_lds_bytes(c->nsb, a.xyw, a.M));
+      lds = std::max(lds, l.scratch ? tdecs16::multi_lds_bytes(ha[k]) : row.lds_bytes(ha[k]));
     }
     if (hipMemcpyAsync(m.d_stage, m.h_stage, need, hipMemcpyHostToDevice, st) != hipSuccess) {
       return SRSRAN_ERROR;
@@ -1076,14 +903,11 @@ int srsran_tdec_gpu_run_multi(uint32_t              nof_groups,
     const TdecArgs* dg = reinterpret_cast<const TdecArgs*>(m.d_stage.get());
     const uint64_t* dk = reinterpret_cast<const uint64_t*>(m.d_stage + abyte);
     const uint32_t* df = reinterpret_cast<const uint32_t*>(m.d_stage + abyte + kbyte);
-    if ((kind == 2   ? (nsbc == 16  ? (w8 ? tdecs16w8::multi_launch(dg, df, (int)n, nblk, lds, st)
-                                          : tdecs16::multi_launch_ck(dg, df, dk, (int)n, nblk, lds, p->d_ck.get(),
-                                                                     p->d_ck.cap(), st))
-                        : nsbc == 8 ? (w8 ? tdecs8w8::multi_launch(dg, df, (int)n, nblk, lds, st)
-                                          : tdecs8::multi_launch(dg, df, (int)n, nblk, lds, st))
-                                    : tdecs1::multi_launch(dg, df, (int)n, nblk, lds, st))
-         : kind == 1 ? tdec16_multi_launch(dg, df, (int)n, nblk, lds, st)
-                     : tdec_multi_launch(cls_nsb[ci], dg, df, (int)n, nblk, lds, st)) != hipSuccess) {
+    // the fused 16-step kernel: checkpoints in p->d_ck
+    const hipError_t e =
+        l.scratch ? tdecs16::multi_launch_ck(dg, df, dk, (int)n, nblk, lds, p->d_ck.get(), p->d_ck.cap(), st)
+                  : row.multi_launch(dg, df, (int)n, nblk, lds, st);
+    if (e != hipSuccess) {
       ret = SRSRAN_ERROR;
     }
   }

@@ -58,7 +58,9 @@ struct TdecArgs {
 static constexpr uint32_t LTE_CRC24A = 0x1864CFB;  // phy_common.h:72
 static constexpr uint32_t LTE_CRC24B = 0x1800063;  // phy_common.h:73
 
-hipError_t tdec_launch(int nsb, const TdecArgs& a, hipStream_t stream);
+// The builds' own launch functions; tdec_dispatch.h chooses among them.
+// tdec_kernel.hip: the quad decoder (four lanes a sub-block) of the nsb-sub-block class
+hipError_t tdec_quad_launch(int nsb, const TdecArgs& a, hipStream_t stream);
 // ngroups descriptors of one decoder class (device array) in one launch; d_first[g] = first
 // workgroup of group g (ascending); lds = the largest tdec_lds_bytes of the groups
 hipError_t tdec_multi_launch(int nsb, const TdecArgs* d_groups, const uint32_t* d_first, int ngroups,
@@ -67,18 +69,13 @@ int        tdec_cpw(int nsb);  // code blocks per workgroup
 
 // tdec16_kernel.hip: the lane-pair decoder of the 16-sub-block class on the SB input layout
 // (every plain / DL-SCH launch of K >= 816 without state save/restore)
-bool       tdec16_eligible(int nsb, const TdecArgs& a);
-bool       tdec16_pays(uint32_t ncb);  // enough blocks in one launch for the lane-pair kernel
-void       tdec16_set_min_cb(uint32_t n);
-uint32_t   tdec16_min_cb();
 hipError_t tdec16_launch(const TdecArgs& a, hipStream_t stream);
 hipError_t tdec16_multi_launch(const TdecArgs* d_groups, const uint32_t* d_first, int ngroups, uint32_t nblocks,
                                size_t lds, hipStream_t stream);
 size_t     tdec16_lds_bytes(const TdecArgs& a);
 int        tdec16_cpw();
 // tdecs_kernel.hip: one lane per sub-block (64 / NSB blocks a workgroup), the window classes of large
-// batches (16 sub-blocks: eligible where tdec16_eligible is, chosen from tdec16s_min_cb() blocks a
-// launch; 8 sub-blocks: tdec8s_eligible)
+// batches
 #define SRSRAN_TDECS_API(ns)                                                                               \
   namespace ns {                                                                                           \
   hipError_t launch(const TdecArgs& a, hipStream_t stream);                                                \
@@ -109,23 +106,6 @@ namespace tdecs8 { hipError_t set_stamps(void* d_buf); }
 namespace tdecs16w8 { hipError_t set_stamps(void* d_buf); }
 namespace tdecs8w8 { hipError_t set_stamps(void* d_buf); }
 #endif
-bool       tdec8s_eligible(int nsb, const TdecArgs& a);
-bool       tdec1s_eligible(int nsb, const TdecArgs& a);
-// srsran_tdec_gpu_set_w8_max_k(): window classes of K up to this size run the 8-step-window build
-void       tdecs_set_w8_max_k(uint32_t k);
-// srsran_tdec_gpu_set_w8_fused_max_k(): the 16-sub-block class's cut in fused multi-size launches
-void       tdecs_set_w8_fused_max_k(uint32_t k);
-uint32_t   tdecs_w8_fused_max_k();
-uint32_t   tdecs_w8_max_k();
-void       tdec8s_set_min_cb(uint32_t n);
-uint32_t   tdec8s_min_cb();
-void       tdec1s_set_min_cb(uint32_t n);
-uint32_t   tdec1s_min_cb();
-void       tdec16s_set_min_cb(uint32_t n);
-uint32_t   tdec16s_min_cb();
-// the kernel the 16-sub-block class runs for a launch of ncb blocks on the SB layout: 2 = single lane
-// per sub-block (tdec16s), 1 = lane pair (tdec16), 0 = quad (tdec_kernel<16>)
-int        tdec16_choice(uint32_t ncb);
 size_t     tdec_lds_bytes(int nsb, int xyw, int M);
 // x^(8m) mod poly for m = 0..nm-1 (host helper for the CRC combine tables)
 void crc24_xpow_table(uint32_t poly, uint32_t* out, int nm);

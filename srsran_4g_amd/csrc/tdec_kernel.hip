@@ -816,21 +816,8 @@ static hipError_t launch(const TdecArgs& a, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t tdec_launch(int nsb, const TdecArgs& a, hipStream_t stream)
+hipError_t tdec_quad_launch(int nsb, const TdecArgs& a, hipStream_t stream)
 {
-  if (a.ncb == 0) {
-    return hipSuccess;
-  }
-  if (tdec16_eligible(nsb, a)) {
-    return tdec16_choice(a.ncb) == 2 ? (a.K <= tdecs_w8_max_k() ? tdecs16w8::launch(a, stream) : tdecs16::launch(a, stream))
-                                     : tdec16_launch(a, stream);
-  }
-  if (tdec8s_eligible(nsb, a)) {
-    return a.K <= tdecs_w8_max_k() ? tdecs8w8::launch(a, stream) : tdecs8::launch(a, stream);
-  }
-  if (tdec1s_eligible(nsb, a)) {
-    return tdecs1::launch(a, stream);
-  }
   switch (nsb) {
     case 16:
       return launch<16>(a, stream);

@@ -174,6 +174,26 @@ def test_gpu_run_multi_mixed_sizes(ora):
         assert np.array_equal(o.cpu().numpy(), w), K
 
 
+def test_gpu_run_multi_natural_layout(ora):
+    """srsran_tdec_gpu_run_multi on the natural input layout: every class fused on its quad kernel."""
+    torch = pytest.importorskip("torch")
+    rng = np.random.default_rng(78)
+    Ks = [40, 48, 408, 416, 816, 832]
+    ins, outs, want = [], [], []
+    for K in Ks:
+        llr = _inputs(ora, K, rng, 3, False)
+        ins.append(torch.from_numpy(llr).cuda())
+        outs.append(torch.zeros((3, K // 8), dtype=torch.uint8, device="cuda"))
+        want.append(ora.run_batch(K, llr, False, 3))
+    stream = torch.cuda.current_stream().cuda_stream
+    tdec.gpu_run_multi(Ks, [t.data_ptr() for t in ins], [t.shape[1] for t in ins], False,
+                       [t.data_ptr() for t in outs], [3] * len(Ks), 3, stream)
+    assert tdec.last_kernel() == "tdec_multi_kernel<1>"  # the generic class is issued last
+    torch.cuda.current_stream().synchronize()
+    for K, o, w in zip(Ks, outs, want):
+        assert np.array_equal(o.cpu().numpy(), w), K
+
+
 def test_config1_full_batch(ora):
     """BASELINE config 1/2 shape: K=6144 x 1024 CBs, 8 half-iterations, AWGN, device-resident."""
     torch = pytest.importorskip("torch")

@@ -1,5 +1,5 @@
 /*
- * include/srsran_ldpc.h -- drop-in C API of the MI355X NR LDPC decoder.
+ * include/srsran_ldpc.h -- drop-in C API of the MI355X NR LDPC decoder, encoder and transmit rate matcher.
  *
  * Replaces the reference interfaces (srsRAN_4G, paths relative to /root/reference/lib):
  *   include/srsran/phy/fec/ldpc/base_graph.h:38-113    srsran_basegraph_t, create_compact_pcm, BG sizes
@@ -22,6 +22,17 @@
  *
  * Added: srsran_ldpc_decoder_gpu_decode_batch(), an asynchronous batch entry point over device
  * buffers on the caller's HIP stream.
+ *
+ * Transmit side:
+ *   include/srsran/phy/fec/ldpc/ldpc_encoder.h:40-118  srsran_ldpc_encoder_{type_t,t},
+ *                                                      srsran_ldpc_encoder_{init,free,encode,encode_rm}
+ *   include/srsran/phy/fec/ldpc/ldpc_rm.h:41-84, 198   srsran_ldpc_rm_t, srsran_ldpc_rm_tx{_init,,_free}
+ * Same names, argument meaning and return values (ldpc_encoder.c:55-97, 511-600, ldpc_rm.c:113-193, 340-360,
+ * 413-434, 582-610); the three encoder types give the same bits in the reference and select the one GPU
+ * encoder.  Differences: srsran_ldpc_rm_tx returns -1 where the reference's init_rm fails (the reference
+ * exits the process), and it expects the filler bytes (254) of its input to form one range, as they do in
+ * every codeword of srsran_ldpc_encoder_encode; otherwise it returns -1.
+ * Added: srsran_ldpc_encoder_gpu_encode_batch(), asynchronous over device buffers.
  */
 #ifndef SRSRAN_AMD_LDPC_H
 #define SRSRAN_AMD_LDPC_H
@@ -147,6 +158,86 @@ int srsran_ldpc_decoder_gpu_decode_batch_s(srsran_ldpc_decoder_t* q,
                                            int                    packed,
                                            uint8_t*               d_ret,
                                            void*                  stream);
+
+/* ---------------- encoder (ldpc_encoder.h:40-118) ---------------- */
+typedef enum {
+  SRSRAN_LDPC_ENCODER_C = 0,
+  SRSRAN_LDPC_ENCODER_AVX2,
+  SRSRAN_LDPC_ENCODER_AVX512,
+} srsran_ldpc_encoder_type_t;
+
+/* ldpc_encoder.h:53-74: the fields callers read; `ptr` holds the GPU context (stream, shift table, staging). */
+typedef struct {
+  void*              ptr;
+  srsran_basegraph_t bg;
+  uint16_t           ls;
+  uint8_t            bgN;
+  uint16_t           liftN;
+  uint8_t            bgM;
+  uint16_t           liftM;
+  uint8_t            bgK;
+  uint16_t           liftK;
+  uint16_t*          pcm;
+  void (*free)(void*);
+  int (*encode)(void*, const uint8_t*, uint8_t*, uint32_t, uint32_t);
+} srsran_ldpc_encoder_t;
+
+/* Host buffers, one bit per byte (254 = filler bit, read as 0 and copied through in the systematic part),
+ * host-synchronous.  0 on success, -1 on an unsupported lifting size or input_length / bgK != ls. */
+int  srsran_ldpc_encoder_init(srsran_ldpc_encoder_t* q, srsran_ldpc_encoder_type_t type, srsran_basegraph_t bg, uint16_t ls); /* ldpc_encoder.c:511 */
+void srsran_ldpc_encoder_free(srsran_ldpc_encoder_t* q);                                                                    /* ldpc_encoder.c:571 */
+int  srsran_ldpc_encoder_encode(srsran_ldpc_encoder_t* q, const uint8_t* input, uint8_t* output, uint32_t input_length);
+/* cdwd_rm_length: clamped to liftN - 2 ls, raised to (bgK + 2) ls, rounded up to a multiple of ls
+ * (ldpc_encoder.c:63-78); that many bytes of output are written, the rest is left alone. */
+int srsran_ldpc_encoder_encode_rm(srsran_ldpc_encoder_t* q,
+                                  const uint8_t*         input,
+                                  uint8_t*               output,
+                                  uint32_t               input_length,
+                                  uint32_t               cdwd_rm_length);
+
+/*
+ * Added batch entry point (asynchronous on `stream`, a hipStream_t; NULL = default stream).
+ *   d_msg  nof_cw x liftK bytes, msg_stride bytes apart (device)
+ *   d_cw   nof_cw codewords, cw_stride bytes apart (device); of each the bytes encode_rm writes for
+ *          cdwd_rm_length are written
+ */
+int srsran_ldpc_encoder_gpu_encode_batch(srsran_ldpc_encoder_t* q,
+                                         const uint8_t*         d_msg,
+                                         uint32_t               msg_stride,
+                                         uint32_t               nof_cw,
+                                         uint32_t               cdwd_rm_length,
+                                         uint8_t*               d_cw,
+                                         uint32_t               cw_stride,
+                                         void*                  stream);
+
+/* ---------------- rate matcher, transmit side (ldpc_rm.h:41-84) ---------------- */
+typedef struct {
+  void*              ptr; /* GPU context (stream, staging) */
+  srsran_basegraph_t bg;
+  uint16_t           ls;
+  uint32_t           N;
+  uint32_t           E;
+  uint32_t           K;
+  uint32_t           F;
+  uint32_t           k0;
+  uint32_t           mod_order;
+  uint32_t           Ncb;
+} srsran_ldpc_rm_t;
+
+/* One code block per call, host buffers, host-synchronous: input = the encoder's codeword (>= Ncb bytes,
+ * filler bytes 254 in place), output = E bytes.  -1 when E % Qm != 0, E > 273 * 13 * 12 * 8 * 4 or the
+ * modulation is invalid. */
+int  srsran_ldpc_rm_tx_init(srsran_ldpc_rm_t* q); /* ldpc_rm.c:413 */
+int  srsran_ldpc_rm_tx(srsran_ldpc_rm_t*        q,
+                       const uint8_t*           input,
+                       uint8_t*                 output,
+                       const uint32_t           E,
+                       const srsran_basegraph_t bg,
+                       const uint32_t           ls,
+                       const uint8_t            rv,
+                       const srsran_mod_t       mod_type,
+                       const uint32_t           Nref); /* ldpc_rm.c:582 */
+void srsran_ldpc_rm_tx_free(srsran_ldpc_rm_t* q);      /* ldpc_rm.c:521 */
 
 #ifdef __cplusplus
 }

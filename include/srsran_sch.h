@@ -6,6 +6,7 @@
  *   lib/include/srsran/phy/fec/crc.h:39-87             srsran_crc_t, srsran_crc_*
  *   lib/include/srsran/phy/fec/turbo/rm_turbo.h:54-87  srsran_rm_turbo_{gentables,free_tables,rx_lut,rx_lut_}
  *   lib/include/srsran/phy/fec/softbuffer.h:41-95      srsran_softbuffer_rx_t, srsran_softbuffer_rx_*
+ *   lib/include/srsran/phy/fec/softbuffer.h:97-134     srsran_softbuffer_tx_t, srsran_softbuffer_tx_{init,init_guru,free,reset}
  *   lib/include/srsran/phy/phch/ra.h:43-53             srsran_ra_tb_t
  *   lib/include/srsran/phy/phch/pdsch_cfg.h:37-71      srsran_pdsch_grant_t, srsran_pdsch_cfg_t
  *   lib/include/srsran/phy/phch/sch.h:52-100           srsran_sch_t, srsran_sch_*, srsran_dlsch_decode{,2}
@@ -146,6 +147,23 @@ int srsran_softbuffer_rx_sync(srsran_softbuffer_rx_t* q);
 int srsran_softbuffer_rx_gpu_arena(int enable, size_t bytes);
 /* added: device address of the soft buffer's first code block (diagnostics) */
 const void* srsran_softbuffer_rx_gpu_ptr(const srsran_softbuffer_rx_t* q);
+
+/* ---------------- transmit soft buffer (softbuffer.h:97-134, softbuffer.c:180-265) ----------------
+ * Different from the reference: the circular buffers are not kept.  The NR transmitter (srsran_sch_nr.h)
+ * encodes from the payload on every call, as the reference does (sch_nr.c:414 refuses data == NULL), keeps
+ * the codeword in on-chip memory and nothing reads the buffer afterwards.  The object therefore carries
+ * only the capacities sch_nr.c:447-462 checks; the buffer_b[] entries are non-NULL placeholders (they
+ * point at no storage and must not be dereferenced), and the reset calls have nothing to clear. */
+typedef struct {
+  uint32_t  max_cb;
+  uint32_t  max_cb_size;
+  uint8_t** buffer_b;
+} srsran_softbuffer_tx_t;
+
+int  srsran_softbuffer_tx_init(srsran_softbuffer_tx_t* q, uint32_t nof_prb);
+int  srsran_softbuffer_tx_init_guru(srsran_softbuffer_tx_t* q, uint32_t max_cb, uint32_t max_cb_size);
+void srsran_softbuffer_tx_free(srsran_softbuffer_tx_t* q);
+void srsran_softbuffer_tx_reset(srsran_softbuffer_tx_t* q);
 
 /* ---------------- grant / PDSCH configuration (ra.h:43-53, pdsch_cfg.h:37-71) ---------------- */
 typedef enum {

@@ -1,5 +1,5 @@
 // srsran_4g_amd/csrc/ldpc_internal.h -- entry points of the LDPC decoder for other modules of the
-// library (NR SCH): code-block mode launches over a decoder object.
+// library (NR SCH): code-block mode launches over a decoder object, and the tables the transmit side shares.
 #ifndef SRSRAN_AMD_LDPC_INTERNAL_H
 #define SRSRAN_AMD_LDPC_INTERNAL_H
 #include <vector>
@@ -17,6 +17,10 @@ int ldpc_launch_cws(srsran_ldpc_decoder_t* q, const LdpcCw* d_cws, uint32_t n, c
                     hipStream_t stream);
 // x^n mod P, n = 0 .. nmax (P with its x^order bit)
 std::vector<uint32_t> ldpc_xpow_table(uint32_t poly, int order, int nmax);
+// the decoder's device table of V mod ls per edge (edge order): the NR SCH transmitter's encoder reads it too
+const uint32_t* ldpc_shift_table(const srsran_ldpc_decoder_t* q);
+// set index of a lifting size (38.212 Table 5.3.2-1), -1 when invalid
+int ldpc_ls_set_index(int ls);
 
 }  // namespace srsran_amd
 #endif

@@ -1,4 +1,4 @@
-// srsran_4g_amd/csrc/nr_sch_api.cpp -- C-ABI host side of the NR SCH receive path on the GPU.
+// srsran_4g_amd/csrc/nr_sch_api.cpp -- C-ABI host side of the NR SCH receive and transmit paths on the GPU.
 //
 // Implements include/srsran_sch_nr.h (the srsran_sch_nr_* / srsran_{dl,ul}sch_nr_decode surface of
 // lib/include/srsran/phy/phch/sch_nr.h) over nr_sch_kernel.hip and the LDPC kernels:
@@ -10,6 +10,12 @@
 // A decode is three launches on the object's stream: rate de-matching of every code block into
 // its (device) soft buffer, one LDPC launch per (base graph, lifting size) with the per-block CRC
 // early stop, and the TB assembly / TB CRC.  No CPU fallback: without a HIP device init fails.
+// Transmit side (nr_sch_tx_kernel.hip):
+//   init_tx                           sch_nr.c:219-281
+//   encode                            sch_nr.c:407-552, 752-777
+// An encode is two launches: the TB CRCs, then every code block of the batch (segmentation, CRC attachment,
+// LDPC encoding and rate matching in one kernel).  The per-(BG, Z) shift tables are the ones the object's
+// LDPC decoder cache keeps.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -23,7 +29,10 @@
 #include "../../include/srsran_sch_nr.h"
 #include "dev_buf.h"
 #include "ldpc_internal.h"
+#include "ldpc_enc_kernel.h"
+#include "nr_rm_tx_pos.h"
 #include "nr_sch_kernel.h"
+#include "nr_sch_tx_kernel.h"
 #include "sch_internal.h"
 
 using namespace srsran_amd;
@@ -165,6 +174,7 @@ struct Stage {
 
 struct Ctx {
   hipStream_t                 stream = nullptr;
+  bool                        tx     = false;  // init_tx: the object encodes; init_rx: it decodes
   srsran_sch_nr_args_t        args{};
   srsran_ldpc_decoder_type_t  dtype  = SRSRAN_LDPC_DECODER_C_AVX2;
   std::map<uint32_t, srsran_ldpc_decoder_t*> dec;  // key: bg << 16 | Z
@@ -178,6 +188,8 @@ struct Ctx {
   DevBuf<int8_t>   d_e;      // host-synchronous calls: staged LLRs / payload / results
   DevBuf<uint8_t>  d_pl;
   DevBuf<uint8_t>  d_res;
+  DevBuf<uint32_t> d_txcrc;  // transmit: one TB CRC accumulator per TB of the last batch
+  DevBuf<uint8_t>  d_eb;     // transmit, host-synchronous calls: staged e_bits
 };
 
 srsran_ldpc_decoder_t* decoder(Ctx* c, srsran_basegraph_t bg, uint32_t Z)
@@ -388,6 +400,10 @@ int decode_sync(srsran_sch_nr_t* q, const srsran_sch_cfg_t* cfg, const srsran_sc
     return SRSRAN_ERROR;
   }
   Ctx*         c  = static_cast<Ctx*>(q->gpu);
+  if (c->tx) {
+    fprintf(stderr, "[srsran_4g_amd] NR SCH: decode needs an object from srsran_sch_nr_init_rx\n");
+    return SRSRAN_ERROR;
+  }
   const size_t ne = tb->nof_bits, npl = (size_t)(tb->tbs > 0 ? tb->tbs : 0) / 8 + 8;
   if (!c->d_e.reserve(ne + 64) || !c->d_pl.reserve(npl) || !c->d_res.reserve(16)) {
     return SRSRAN_ERROR;
@@ -420,6 +436,185 @@ int decode_sync(srsran_sch_nr_t* q, const srsran_sch_cfg_t* cfg, const srsran_sc
     all = all && tb->softbuffer.rx->cb_crc[r];
   }
   if (all && hipMemcpy(res->payload, c->d_pl, (size_t)tb->tbs / 8, hipMemcpyDeviceToHost) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+
+constexpr uint32_t kRmMaxE = 273 * 13 * 12 * 8 * 4;  // MAXE, ldpc_rm.c:77
+
+// one descriptor upload through the object's pinned, double-buffered staging
+int upload_desc(Ctx* c, const void* a, size_t na, const void* b, size_t nb, size_t off_b, hipStream_t stream)
+{
+  Stage& st = c->stage[c->cur];
+  c->cur ^= 1;
+  if (st.used && hipEventSynchronize(st.ev) != hipSuccess) {  // its previous upload has been consumed
+    return SRSRAN_ERROR;
+  }
+  const size_t total = off_b + nb;
+  if (!st.h.reserve(total)) {
+    return SRSRAN_ERROR;
+  }
+  if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  memcpy(st.h, a, na);
+  memcpy(st.h + off_b, b, nb);
+  if (hipMemcpyAsync(c->d_desc, st.h, total, hipMemcpyHostToDevice, stream) != hipSuccess ||
+      hipEventRecord(st.ev, stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  st.used = true;
+  return SRSRAN_SUCCESS;
+}
+
+// sch_nr.c:407-552 for n TBs: checks in the reference's order, then the TB CRC launch and the code block launch
+int encode_batch(srsran_sch_nr_t* q, uint32_t n, const srsran_sch_nr_gpu_enc_t* in, hipStream_t stream)
+{
+  Ctx* c = static_cast<Ctx*>(q->gpu);
+  std::vector<NrTxTb> tb;
+  std::vector<NrTxCb> cb;
+  uint32_t            slices = 1, max_ls = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const srsran_sch_tb_t* t = in[i].tb;
+    if (!t || !in[i].sch_cfg || !in[i].d_payload || !in[i].d_e_bits) {
+      return SRSRAN_ERROR_INVALID_INPUTS;
+    }
+    if (!t->softbuffer.tx) {
+      fprintf(stderr, "[srsran_4g_amd] NR SCH: missing Tx softbuffer\n");
+      return SRSRAN_ERROR;
+    }
+    srsran_sch_nr_tb_info_t info;
+    if (srsran_sch_nr_fill_tb_info(&q->carrier, in[i].sch_cfg, t, &info) != SRSRAN_SUCCESS) {
+      return SRSRAN_ERROR;  // includes C > SRSRAN_SCH_NR_MAX_NOF_CB_LDPC
+    }
+    if (!c->tx) {  // the reference finds its encoder pointers NULL (sch_nr.c:436-439)
+      fprintf(stderr, "[srsran_4g_amd] NR SCH: encode needs an object from srsran_sch_nr_init_tx\n");
+      return SRSRAN_ERROR;
+    }
+    const srsran_softbuffer_tx_t* sb  = t->softbuffer.tx;
+    const uint32_t                bgN = info.bg == BG1 ? 66u : 50u;  // liftN / Z less the two punctured columns
+    if (sb->max_cb < info.C) {  // sch_nr.c:448-454
+      fprintf(stderr, "[srsran_4g_amd] NR SCH: soft buffer of %u code blocks for C=%u\n", sb->max_cb, info.C);
+      return SRSRAN_ERROR;
+    }
+    if (sb->max_cb_size < info.Z * bgN) {  // sch_nr.c:456-462
+      fprintf(stderr, "[srsran_4g_amd] NR SCH: soft buffer code block size %u, requires %u\n", sb->max_cb_size,
+              info.Z * bgN);
+      return SRSRAN_ERROR;
+    }
+    const uint32_t cb_len = info.Kp - info.L_cb;
+    if (info.C == 0 || info.A % 8u || (info.C > 1 && cb_len % 8u)) {
+      fprintf(stderr, "[srsran_4g_amd] NR SCH: TBS %u with %u code blocks of %u bits is not byte aligned\n", info.A,
+              info.C, cb_len);
+      return SRSRAN_ERROR;
+    }
+    if (info.Qm == 0 || info.Nl == 0 || info.Kp < 2 * info.Z) {
+      return SRSRAN_ERROR;
+    }
+    srsran_ldpc_decoder_t* dec = decoder(c, info.bg, info.Z);  // its shift table serves the encoder too
+    if (!dec) {
+      return SRSRAN_ERROR;
+    }
+    uint32_t k0, Ncb;
+    nr_rm_tx_k0_ncb(info.bg == BG1 ? 0 : 1, info.Z, (uint32_t)t->rv & 3u, info.Nref, &k0, &Ncb);
+    const NrRmTxSel sel = nr_rm_tx_sel(k0, Ncb, info.Kp - 2 * info.Z, info.Kr - 2 * info.Z);
+    const NrSchE    e   = nr_sch_E(info.G, info.Nl, info.Qm, info.Cp);
+    if (sel.L == 0 || e.E1 > kRmMaxE) {
+      return SRSRAN_ERROR;
+    }
+    NrTxTb d  = {};
+    d.payload = in[i].d_payload;
+    d.crc     = reinterpret_cast<uint32_t*>((size_t)i);  // patched after allocation
+    d.nbytes  = info.A / 8u;
+    d.L_tb    = info.L_tb;
+    tb.push_back(d);
+    slices = std::max(slices, (d.nbytes + NR_TB_SLICE - 1) / NR_TB_SLICE);
+    max_ls = std::max(max_ls, info.Z);
+    for (uint32_t r = 0; r < info.C; r++) {
+      const bool     last = r == info.C - 1;
+      const uint32_t E    = nr_sch_E_of(e, r);
+      // the rows the transmitted span reaches: up to the last selected position, or the whole circle when
+      // the selection wraps (fillers inside the span push it beyond k0 + E)
+      const uint32_t span = E == 0 ? 0u : (E > sel.lap1 ? Ncb : nr_rm_tx_pos(sel, E - 1) + 1u);
+      NrTxCb         b    = {};
+      b.payload           = in[i].d_payload;
+      b.e                 = in[i].d_e_bits + nr_sch_E_offset(e, r);
+      b.tb_crc            = d.crc;
+      b.sh                = ldpc_shift_table(dec);
+      b.inv_L             = ((1ull << 40) + sel.L - 1) / sel.L;
+      b.byte0             = r * (cb_len / 8u);
+      b.data_bytes        = (last ? cb_len - info.L_tb : cb_len) / 8u;
+      b.L_tb              = last ? info.L_tb : 0u;
+      b.L_cb              = info.L_cb;
+      b.E                 = E;
+      b.Qm                = info.Qm;
+      b.magic_ls          = (uint32_t)((0x100000000ull + info.Z - 1) / info.Z);
+      b.Z                 = (uint16_t)info.Z;
+      b.n_rows            = (uint16_t)ldpc_layers_for(dec, span);
+      b.bg                = info.bg == BG1 ? 0 : 1;
+      b.hr_case           = (uint8_t)ldpc_enc_hr_case(b.bg, ldpc_ls_set_index((int)info.Z));
+      b.sel               = sel;
+      cb.push_back(b);
+    }
+  }
+  if (n == 0) {
+    return SRSRAN_SUCCESS;
+  }
+  if (slices > NR_TB_MAX_SLICES) {
+    return SRSRAN_ERROR;
+  }
+  const size_t sz_tb = (sizeof(NrTxTb) * n + 15) & ~size_t(15);
+  const size_t sz_cb = sizeof(NrTxCb) * cb.size();
+  if (!c->d_desc.reserve(sz_tb + sz_cb) || !c->d_txcrc.reserve(n)) {
+    return SRSRAN_ERROR;
+  }
+  for (auto& d : tb) {
+    d.crc = c->d_txcrc + reinterpret_cast<size_t>(d.crc);
+  }
+  for (auto& b : cb) {
+    b.tb_crc = c->d_txcrc + reinterpret_cast<size_t>(b.tb_crc);
+  }
+  const NrTxTb* d_tb = reinterpret_cast<const NrTxTb*>(c->d_desc.get());
+  const NrTxCb* d_cb = reinterpret_cast<const NrTxCb*>(c->d_desc + sz_tb);
+  if (hipMemsetAsync(c->d_txcrc, 0, sizeof(uint32_t) * n, stream) != hipSuccess ||
+      upload_desc(c, tb.data(), sizeof(NrTxTb) * n, cb.data(), sz_cb, sz_tb, stream) != SRSRAN_SUCCESS ||
+      nr_tb_crc_launch(d_tb, n, slices, stream) != hipSuccess ||
+      nr_tx_cb_launch(d_cb, (uint32_t)cb.size(), c->d_xpow[0], max_ls, stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  return SRSRAN_SUCCESS;
+}
+
+int encode_sync(srsran_sch_nr_t* q, const srsran_sch_cfg_t* cfg, const srsran_sch_tb_t* tb, const uint8_t* data,
+                uint8_t* e_bits)
+{
+  if (!q || !q->gpu || !cfg || !tb || !data || !e_bits) {  // sch_nr.c:414-416
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  Ctx*         c   = static_cast<Ctx*>(q->gpu);
+  const size_t npl = (size_t)(tb->tbs > 0 ? tb->tbs : 0) / 8, ne = tb->nof_bits;
+  if (!c->d_pl.reserve(npl + 8) || !c->d_eb.reserve(ne + 8)) {
+    return SRSRAN_ERROR;
+  }
+  if (hipMemcpyAsync(c->d_pl, data, npl, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+    return SRSRAN_ERROR;
+  }
+  const srsran_sch_nr_gpu_enc_t one = {cfg, tb, c->d_pl, c->d_eb};
+  const int                     r   = encode_batch(q, 1, &one, c->stream);
+  if (r != SRSRAN_SUCCESS) {
+    hipStreamSynchronize(c->stream);  // `data` is the caller's again
+    return r;
+  }
+  // the reference writes the sum of the blocks' E, which can stop short of nof_bits (sch_nr.c:534-548)
+  srsran_sch_nr_tb_info_t info;
+  if (srsran_sch_nr_fill_tb_info(&q->carrier, cfg, tb, &info) != SRSRAN_SUCCESS) {
+    return SRSRAN_ERROR;
+  }
+  const size_t total = nr_sch_E_offset(nr_sch_E(info.G, info.Nl, info.Qm, info.Cp), info.C);
+  if (total > ne || hipMemcpyAsync(e_bits, c->d_eb, total, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
     return SRSRAN_ERROR;
   }
   return SRSRAN_SUCCESS;
@@ -486,13 +681,13 @@ int srsran_sch_nr_fill_tb_info(const srsran_carrier_nr_t* carrier,
   return SRSRAN_SUCCESS;
 }
 
-int srsran_sch_nr_init_rx(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args)
+static int init_common(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args, bool tx)
 {
   if (!q || !args) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   memset(q, 0, sizeof(*q));
-  if (args->decoder_use_flooded) {
+  if (!tx && args->decoder_use_flooded) {
     fprintf(stderr, "[srsran_4g_amd] NR SCH: flooded LDPC schedule not provided on the GPU\n");
     return SRSRAN_ERROR;
   }
@@ -503,6 +698,7 @@ int srsran_sch_nr_init_rx(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args)
     return SRSRAN_ERROR;
   }
   Ctx* c   = new Ctx;
+  c->tx    = tx;
   c->args  = *args;
   c->dtype = args->disable_simd ? SRSRAN_LDPC_DECODER_C : SRSRAN_LDPC_DECODER_C_AVX2;  // sch_nr.c:290-300
   const uint32_t polys[3] = {kCrc24b, kCrc24a, kCrc16};
@@ -520,6 +716,11 @@ int srsran_sch_nr_init_rx(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args)
   }
   return SRSRAN_SUCCESS;
 }
+
+int srsran_sch_nr_init_rx(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args) { return init_common(q, args, false); }
+
+// sch_nr.c:219-281: the reference builds an encoder per lifting size here; the tables are made on first use
+int srsran_sch_nr_init_tx(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args) { return init_common(q, args, true); }
 
 int srsran_sch_nr_set_carrier(srsran_sch_nr_t* q, const srsran_carrier_nr_t* carrier)
 {
@@ -584,7 +785,36 @@ int srsran_sch_nr_gpu_decode_batch(srsran_sch_nr_t*              q,
   if (!q || !q->gpu || (nof_tb && (!tbs || !d_crc || !d_avg_iter))) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
+  if (static_cast<Ctx*>(q->gpu)->tx) {
+    return SRSRAN_ERROR;
+  }
   return decode_batch(q, nof_tb, tbs, d_crc, d_avg_iter, static_cast<hipStream_t>(stream));
+}
+
+int srsran_dlsch_nr_encode(srsran_sch_nr_t*        q,
+                           const srsran_sch_cfg_t* sch_cfg,
+                           const srsran_sch_tb_t*  tb,
+                           const uint8_t*          data,
+                           uint8_t*                e_bits)
+{
+  return encode_sync(q, sch_cfg, tb, data, e_bits);
+}
+
+int srsran_ulsch_nr_encode(srsran_sch_nr_t*        q,
+                           const srsran_sch_cfg_t* sch_cfg,
+                           const srsran_sch_tb_t*  tb,
+                           const uint8_t*          data,
+                           uint8_t*                e_bits)
+{
+  return encode_sync(q, sch_cfg, tb, data, e_bits);
+}
+
+int srsran_sch_nr_gpu_encode_batch(srsran_sch_nr_t* q, uint32_t nof_tb, const srsran_sch_nr_gpu_enc_t* tbs, void* stream)
+{
+  if (!q || !q->gpu || (nof_tb && !tbs)) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  return encode_batch(q, nof_tb, tbs, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nr_tb_crc.h"
+
 namespace srsran_amd {
 
 // One code block's rate de-matching (srsran_ldpc_rm_rx_c, ldpc_rm.c:675-706) into its soft buffer.
@@ -31,11 +33,7 @@ struct NrTb {
   uint32_t       data_stride, C, A, Kp, L_cb, L_tb;
 };
 
-// TB assembly slices: each workgroup copies and CRCs NR_TB_SLICE payload bytes of one TB
-constexpr uint32_t NR_TB_THREADS = 256;
-constexpr uint32_t NR_TB_BYTES   = 16;  // contiguous bytes per thread
-constexpr uint32_t NR_TB_SLICE   = NR_TB_THREADS * NR_TB_BYTES;
-
+// TB assembly slices (nr_tb_crc.h): each workgroup copies and CRCs NR_TB_SLICE payload bytes of one TB
 hipError_t nr_rm_launch(const NrRmCb* d_cbs, uint32_t ncb, hipStream_t stream);
 // slices = max over the TBs of ceil(payload bytes / NR_TB_SLICE) (at least 1)
 hipError_t nr_tb_launch(const NrTb* d_tbs, uint32_t ntb, uint32_t slices, hipStream_t stream);

@@ -158,47 +158,7 @@ __global__ __launch_bounds__(256) void nr_rm_kernel(const NrRmCb* __restrict__ c
   }
 }
 
-// a * b mod P, P of degree `order` <= 24 given with its x^order bit, a, b < 2^order (Horner over
-// the 24 low bits of b: leading zero bits leave r = 0)
-__host__ __device__ constexpr uint32_t mulmod(uint32_t a, uint32_t b, uint32_t poly, int order)
-{
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 23; i >= 0; i--) {
-    r = (r << 1) ^ (((b >> i) & 1u) ? a : 0u);
-    r ^= ((r >> order) & 1u) ? poly : 0u;
-  }
-  return r;
-}
-
-// Shift factors of the TB CRCs ([0] CRC24A, [1] CRC16, phy_common.h:72-74): thread[t] = x^(8 16 t)
-// and slice[s] = x^(8 NR_TB_SLICE s) mod P -- the bytes after a thread's chunk inside its slice and
-// after the slice
-struct TbCrcShift {
-  uint32_t thread[2][NR_TB_THREADS];
-  uint32_t slice[2][16];
-  constexpr TbCrcShift() : thread(), slice()
-  {
-    const uint32_t polys[2] = {0x1864CFBu, 0x11021u};
-    const int      ords[2]  = {24, 16};
-    for (int t = 0; t < 2; t++) {
-      uint32_t x128 = 1u << 8;  // x^8 -> x^128
-      for (int k = 0; k < 4; k++) {
-        x128 = mulmod(x128, x128, polys[t], ords[t]);
-      }
-      thread[t][0] = 1u;
-      for (uint32_t i = 1; i < NR_TB_THREADS; i++) {
-        thread[t][i] = mulmod(thread[t][i - 1], x128, polys[t], ords[t]);
-      }
-      const uint32_t xs = mulmod(thread[t][NR_TB_THREADS - 1], x128, polys[t], ords[t]);  // x^(8 16 256)
-      slice[t][0]       = 1u;
-      for (int i = 1; i < 16; i++) {
-        slice[t][i] = mulmod(slice[t][i - 1], xs, polys[t], ords[t]);
-      }
-    }
-  }
-};
-static_assert(NR_TB_SLICE == 16 * NR_TB_THREADS, "slice = threads x 16 bytes");
+// shift factors of the TB CRCs (nr_tb_crc.h)
 __constant__ TbCrcShift c_tb_shift = TbCrcShift();
 
 // Grid (TB, slice).  Every slice checks the blocks' flags itself.  Counted from the end of the payload,
@@ -246,14 +206,7 @@ __global__ __launch_bounds__(NR_TB_THREADS) void nr_tb_kernel(const NrTb* __rest
   const int      order = (int)d.L_tb;
   const uint32_t mask  = (1u << order) - 1u;
   if (tbcrc) {
-    for (uint32_t v = threadIdx.x; v < 256; v += blockDim.x) {
-      uint32_t c = v << (order - 8);
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        c = (c & (1u << (order - 1))) ? ((c << 1) ^ poly) : (c << 1);
-      }
-      s_tab[v] = c & mask;
-    }
+    tb_crc_table(s_tab, poly, order);
   }
   // chunks are counted from the end of the payload: thread t of slice s holds the 16 bytes that end
   // 16 t + NR_TB_SLICE s bytes before it (the first chunk of the payload may be shorter)

@@ -937,6 +937,45 @@ int srsran_softbuffer_rx_init(srsran_softbuffer_rx_t* q, uint32_t nof_prb)
   return srsran_softbuffer_rx_init_guru(q, max_cb, SOFTBUFFER_SIZE);
 }
 
+// ---------------- softbuffer.c:180-265: capacities only (include/srsran_sch.h) ----------------
+int srsran_softbuffer_tx_init(srsran_softbuffer_tx_t* q, uint32_t nof_prb)
+{
+  if (nof_prb == 0 || nof_prb > SRSRAN_MAX_PRB) {
+    return SRSRAN_ERROR;
+  }
+  const uint32_t max_cb = (uint32_t)kTbsMaxIdx[nof_prb - 1] / (SRSRAN_TCOD_MAX_LEN_CB - 24) + 1;
+  return srsran_softbuffer_tx_init_guru(q, max_cb, SOFTBUFFER_SIZE);
+}
+
+int srsran_softbuffer_tx_init_guru(srsran_softbuffer_tx_t* q, uint32_t max_cb, uint32_t max_cb_size)
+{
+  if (!q) {
+    return SRSRAN_ERROR_INVALID_INPUTS;
+  }
+  memset(q, 0, sizeof(*q));
+  q->max_cb      = max_cb;
+  q->max_cb_size = max_cb_size;
+  q->buffer_b    = (uint8_t**)calloc(max_cb ? max_cb : 1, sizeof(uint8_t*));
+  if (!q->buffer_b) {
+    memset(q, 0, sizeof(*q));
+    return SRSRAN_ERROR;
+  }
+  for (uint32_t i = 0; i < max_cb; i++) {
+    q->buffer_b[i] = reinterpret_cast<uint8_t*>(q->buffer_b);  // placeholder: non-NULL, never dereferenced
+  }
+  return SRSRAN_SUCCESS;
+}
+
+void srsran_softbuffer_tx_free(srsran_softbuffer_tx_t* q)
+{
+  if (q) {
+    free(q->buffer_b);
+    memset(q, 0, sizeof(*q));
+  }
+}
+
+void srsran_softbuffer_tx_reset(srsran_softbuffer_tx_t* q) { (void)q; }
+
 int srsran_softbuffer_rx_init_guru(srsran_softbuffer_rx_t* q, uint32_t max_cb, uint32_t max_cb_size)
 {
   if (!q) {

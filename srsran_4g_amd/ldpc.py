@@ -1,8 +1,9 @@
-"""Python mirror of the srsran_ldpc_decoder_* C API (include/srsran_ldpc.h).
+"""Python mirror of the srsran_ldpc_decoder_* / srsran_ldpc_encoder_* / srsran_ldpc_rm_tx* C API
+(include/srsran_ldpc.h).
 
-Binds the C-ABI library with ctypes so tests and bench.py drive the GPU NR LDPC decoder the way
-the reference's own tests drive lib/src/phy/fec/ldpc/ldpc_decoder.c (ldpc_dec_avx2_test.c,
-ldpc_rm_chain_test.c).  There is no Python or CPU fallback: without the library or a HIP device
+Binds the C-ABI library with ctypes so tests and bench.py drive the GPU NR LDPC decoder, encoder and
+transmit rate matcher the way the reference's own tests drive lib/src/phy/fec/ldpc (ldpc_dec_avx2_test.c,
+ldpc_enc_test.c, ldpc_rm_chain_test.c).  There is no Python or CPU fallback: without the library or a HIP device
 the calls raise.
 """
 import ctypes
@@ -33,6 +34,22 @@ class srsran_ldpc_decoder_t(ctypes.Structure):
                 ("decode_f", ctypes.c_void_p), ("decode_s", ctypes.c_void_p), ("decode_c", ctypes.c_void_p)]
 
 
+ENC_C, ENC_AVX2, ENC_AVX512 = range(3)  # ldpc_encoder.h:40-48
+
+
+class srsran_ldpc_encoder_t(ctypes.Structure):
+    _fields_ = [("ptr", ctypes.c_void_p), ("bg", ctypes.c_int), ("ls", ctypes.c_uint16), ("bgN", ctypes.c_uint8),
+                ("liftN", ctypes.c_uint16), ("bgM", ctypes.c_uint8), ("liftM", ctypes.c_uint16),
+                ("bgK", ctypes.c_uint8), ("liftK", ctypes.c_uint16), ("pcm", ctypes.POINTER(ctypes.c_uint16)),
+                ("free", ctypes.c_void_p), ("encode", ctypes.c_void_p)]
+
+
+class srsran_ldpc_rm_t(ctypes.Structure):
+    _fields_ = [("ptr", ctypes.c_void_p), ("bg", ctypes.c_int), ("ls", ctypes.c_uint16), ("N", ctypes.c_uint32),
+                ("E", ctypes.c_uint32), ("K", ctypes.c_uint32), ("F", ctypes.c_uint32), ("k0", ctypes.c_uint32),
+                ("mod_order", ctypes.c_uint32), ("Ncb", ctypes.c_uint32)]
+
+
 _sig = False
 
 
@@ -55,6 +72,20 @@ def _lib():
                                                            ctypes.POINTER(srsran_crc_t), P, ctypes.c_uint32,
                                                            ctypes.c_int, P, P]
         L.srsran_ldpc_decoder_gpu_decode_batch_s.argtypes = L.srsran_ldpc_decoder_gpu_decode_batch.argtypes
+        E = ctypes.POINTER(srsran_ldpc_encoder_t)
+        L.srsran_ldpc_encoder_init.argtypes = [E, ctypes.c_int, ctypes.c_int, ctypes.c_uint16]
+        L.srsran_ldpc_encoder_free.argtypes = [E]
+        L.srsran_ldpc_encoder_free.restype = None
+        L.srsran_ldpc_encoder_encode.argtypes = [E, P, P, ctypes.c_uint32]
+        L.srsran_ldpc_encoder_encode_rm.argtypes = [E, P, P, ctypes.c_uint32, ctypes.c_uint32]
+        L.srsran_ldpc_encoder_gpu_encode_batch.argtypes = [E, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P,
+                                                           ctypes.c_uint32, P]
+        R = ctypes.POINTER(srsran_ldpc_rm_t)
+        L.srsran_ldpc_rm_tx_init.argtypes = [R]
+        L.srsran_ldpc_rm_tx_free.argtypes = [R]
+        L.srsran_ldpc_rm_tx_free.restype = None
+        L.srsran_ldpc_rm_tx.argtypes = [R, P, P, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint8,
+                                        ctypes.c_int, ctypes.c_uint32]
         L.create_compact_pcm.argtypes = [P, P, ctypes.c_int, ctypes.c_uint16]
         L.srsran_crc_init.argtypes = [ctypes.POINTER(srsran_crc_t), ctypes.c_uint32, ctypes.c_int]
         _sig = True
@@ -127,3 +158,74 @@ class LdpcDecoder:
         return fn(
             ctypes.byref(self.q), d_llrs, llr_stride, nof_cw, self.n_llr if length is None else length,
             ctypes.byref(c) if c is not None else None, d_message, message_stride, int(packed), d_ret, stream)
+
+
+class LdpcEncoder:
+    """srsran_ldpc_encoder_t on the GPU (one HIP stream per object).  Buffers are one bit per byte; 254 marks a
+    filler bit."""
+
+    def __init__(self, bg, ls, etype=ENC_AVX2):
+        self.q = srsran_ldpc_encoder_t()
+        if _lib().srsran_ldpc_encoder_init(ctypes.byref(self.q), etype, bg, ls) != 0:
+            raise RuntimeError("srsran_ldpc_encoder_init failed (no HIP device, or unsupported lifting size)")
+        self.bg, self.ls = bg, ls
+        M, N, K = BG_SHAPE[bg]
+        self.liftK, self.n_cw = K * ls, (N - 2) * ls
+
+    def free(self):
+        if self.q.ptr:
+            _lib().srsran_ldpc_encoder_free(ctypes.byref(self.q))
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def encode(self, msg, input_length=None):
+        """srsran_ldpc_encoder_encode of one message: (return value, codeword of liftN - 2 ls bytes)."""
+        msg = np.ascontiguousarray(msg, np.uint8)
+        out = np.zeros(self.n_cw, np.uint8)
+        r = _lib().srsran_ldpc_encoder_encode(ctypes.byref(self.q), msg.ctypes.data, out.ctypes.data,
+                                              msg.size if input_length is None else input_length)
+        return r, out
+
+    def encode_rm(self, msg, cdwd_rm_length, fill=0):
+        """srsran_ldpc_encoder_encode_rm into a buffer of liftN - 2 ls bytes preset to `fill`."""
+        msg = np.ascontiguousarray(msg, np.uint8)
+        out = np.full(self.n_cw, fill, np.uint8)
+        r = _lib().srsran_ldpc_encoder_encode_rm(ctypes.byref(self.q), msg.ctypes.data, out.ctypes.data, msg.size,
+                                                 cdwd_rm_length)
+        return r, out
+
+    def encode_batch(self, d_msg, msg_stride, nof_cw, d_cw, cw_stride, length=None, stream=None):
+        """Asynchronous batch over device pointers (ints); returns the C status."""
+        return _lib().srsran_ldpc_encoder_gpu_encode_batch(
+            ctypes.byref(self.q), d_msg, msg_stride, nof_cw, self.n_cw if length is None else length, d_cw,
+            cw_stride, stream)
+
+
+class LdpcRmTx:
+    """srsran_ldpc_rm_t, transmit side: one code block per call, host-synchronous."""
+
+    def __init__(self):
+        self.q = srsran_ldpc_rm_t()
+        if _lib().srsran_ldpc_rm_tx_init(ctypes.byref(self.q)) != 0:
+            raise RuntimeError("srsran_ldpc_rm_tx_init failed (no HIP device?)")
+
+    def free(self):
+        if self.q.ptr:
+            _lib().srsran_ldpc_rm_tx_free(ctypes.byref(self.q))
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def rm_tx(self, cw, E, bg, ls, rv, mod, Nref, fill=0):
+        """srsran_ldpc_rm_tx: (return value, E output bytes preset to `fill`)."""
+        cw = np.ascontiguousarray(cw, np.uint8)
+        out = np.full(max(E, 1), fill, np.uint8)
+        r = _lib().srsran_ldpc_rm_tx(ctypes.byref(self.q), cw.ctypes.data, out.ctypes.data, E, bg, ls, rv, mod, Nref)
+        return r, out[:E]

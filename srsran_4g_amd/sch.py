@@ -43,6 +43,10 @@ class srsran_softbuffer_rx_t(ctypes.Structure):
                 ("tb_crc", ctypes.c_bool), ("gpu", ctypes.c_void_p)]
 
 
+class srsran_softbuffer_tx_t(ctypes.Structure):  # capacities only (include/srsran_sch.h)
+    _fields_ = [("max_cb", u32), ("max_cb_size", u32), ("buffer_b", ctypes.POINTER(ctypes.c_void_p))]
+
+
 class srsran_ra_tb_t(ctypes.Structure):
     _fields_ = [("mod", ctypes.c_int), ("tbs", ctypes.c_int), ("rv", ctypes.c_int), ("nof_bits", u32),
                 ("cw_idx", u32), ("enabled", ctypes.c_bool), ("mcs_idx", u32)]
@@ -220,6 +224,10 @@ def lib():
         "srsran_softbuffer_rx_sync": ([SB], ctypes.c_int),
         "srsran_softbuffer_rx_gpu_arena": ([ctypes.c_int, ctypes.c_size_t], ctypes.c_int),
         "srsran_softbuffer_rx_gpu_ptr": ([SB], ctypes.c_void_p),
+        "srsran_softbuffer_tx_init": ([ctypes.POINTER(srsran_softbuffer_tx_t), u32], ctypes.c_int),
+        "srsran_softbuffer_tx_init_guru": ([ctypes.POINTER(srsran_softbuffer_tx_t), u32, u32], ctypes.c_int),
+        "srsran_softbuffer_tx_reset": ([ctypes.POINTER(srsran_softbuffer_tx_t)], None),
+        "srsran_softbuffer_tx_free": ([ctypes.POINTER(srsran_softbuffer_tx_t)], None),
         "srsran_sch_init": ([SCH], ctypes.c_int),
         "srsran_sch_free": ([SCH], None),
         "srsran_sch_set_max_noi": ([SCH, u32], None),
@@ -344,6 +352,32 @@ class SoftbufferRx:
     def free(self):
         if self.s.gpu:
             lib().srsran_softbuffer_rx_free(ctypes.byref(self.s))
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class SoftbufferTx:
+    """srsran_softbuffer_tx_t owner: the capacities the NR transmitter checks (no circular buffer is kept)."""
+
+    def __init__(self, nof_prb=None, max_cb=None, max_cb_size=SOFTBUFFER_SIZE):
+        self.s = srsran_softbuffer_tx_t()
+        if nof_prb is not None:
+            ret = lib().srsran_softbuffer_tx_init(ctypes.byref(self.s), nof_prb)
+        else:
+            ret = lib().srsran_softbuffer_tx_init_guru(ctypes.byref(self.s), max_cb, max_cb_size)
+        if ret != 0:
+            raise RuntimeError(f"srsran_softbuffer_tx_init failed ({ret})")
+
+    def reset(self):
+        lib().srsran_softbuffer_tx_reset(ctypes.byref(self.s))
+
+    def free(self):
+        if self.s.buffer_b:
+            lib().srsran_softbuffer_tx_free(ctypes.byref(self.s))
 
     def __del__(self):
         try:

@@ -1,14 +1,16 @@
-"""Python mirror of the NR shared-channel receive API (include/srsran_sch_nr.h).
+"""Python mirror of the NR shared-channel API (include/srsran_sch_nr.h), receive and transmit.
 
-Binds LDPC code block segmentation, TB info (sch_nr.c:114-176), and the DL-SCH / UL-SCH decoders
-(sch_nr.c:554-750) of the in-tree HIP library, the way the reference's pdsch_nr_test.c /
-sch_nr_test.c drive srsran_dlsch_nr_decode.  No CPU fallback: every decode runs the HIP kernels.
+Binds LDPC code block segmentation, TB info (sch_nr.c:114-176), the DL-SCH / UL-SCH decoders
+(sch_nr.c:554-750) and encoders (sch_nr.c:407-552) of the in-tree HIP library, the way the reference's
+pdsch_nr_test.c / sch_nr_test.c drive srsran_dlsch_nr_decode / _encode.  No CPU fallback: every decode and
+encode runs the HIP kernels.
 """
 import ctypes
 
 import numpy as np
 
-from .sch import MOD_FROM_QM, SoftbufferRx, _memcpy_d2h, srsran_cbsegm_t, srsran_softbuffer_rx_t
+from .sch import (MOD_FROM_QM, SoftbufferRx, SoftbufferTx, _memcpy_d2h, srsran_cbsegm_t, srsran_softbuffer_rx_t,
+                  srsran_softbuffer_tx_t)
 from .tdec import load_library
 
 u32 = ctypes.c_uint32
@@ -29,7 +31,7 @@ class srsran_sch_cfg_t(ctypes.Structure):
 
 
 class _sch_softbuffer(ctypes.Union):
-    _fields_ = [("tx", ctypes.c_void_p), ("rx", ctypes.POINTER(srsran_softbuffer_rx_t))]
+    _fields_ = [("tx", ctypes.POINTER(srsran_softbuffer_tx_t)), ("rx", ctypes.POINTER(srsran_softbuffer_rx_t))]
 
 
 class srsran_sch_tb_t(ctypes.Structure):
@@ -69,6 +71,11 @@ class srsran_sch_nr_gpu_tb_t(ctypes.Structure):
                 ("d_e_bits", ctypes.c_void_p), ("d_payload", ctypes.c_void_p), ("new_data", u32)]
 
 
+class srsran_sch_nr_gpu_enc_t(ctypes.Structure):
+    _fields_ = [("sch_cfg", ctypes.POINTER(srsran_sch_cfg_t)), ("tb", ctypes.POINTER(srsran_sch_tb_t)),
+                ("d_payload", ctypes.c_void_p), ("d_e_bits", ctypes.c_void_p)]
+
+
 _bound = False
 
 
@@ -89,6 +96,11 @@ def lib():
         "srsran_sch_nr_fill_tb_info": ([ctypes.POINTER(srsran_carrier_nr_t), CFG, TB,
                                         ctypes.POINTER(srsran_sch_nr_tb_info_t)], ctypes.c_int),
         "srsran_sch_nr_init_rx": ([Q, ctypes.POINTER(srsran_sch_nr_args_t)], ctypes.c_int),
+        "srsran_sch_nr_init_tx": ([Q, ctypes.POINTER(srsran_sch_nr_args_t)], ctypes.c_int),
+        "srsran_dlsch_nr_encode": ([Q, CFG, TB, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+        "srsran_ulsch_nr_encode": ([Q, CFG, TB, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+        "srsran_sch_nr_gpu_encode_batch": ([Q, u32, ctypes.POINTER(srsran_sch_nr_gpu_enc_t), ctypes.c_void_p],
+                                           ctypes.c_int),
         "srsran_sch_nr_set_carrier": ([Q, ctypes.POINTER(srsran_carrier_nr_t)], ctypes.c_int),
         "srsran_sch_nr_free": ([Q], None),
         "srsran_dlsch_nr_decode": ([Q, CFG, TB, i8p, RES], ctypes.c_int),
@@ -140,7 +152,9 @@ def make_tb(tbs, R, Qm, G, Nl, rv=0, softbuffer=None):
     tb.nof_bits = G
     tb.nof_re = G // (Qm * Nl)
     tb.enabled = True
-    if softbuffer is not None:
+    if isinstance(softbuffer, SoftbufferTx):
+        tb.softbuffer.tx = ctypes.pointer(softbuffer.s)
+    elif softbuffer is not None:
         tb.softbuffer.rx = ctypes.pointer(softbuffer.s)
     return tb
 
@@ -163,6 +177,11 @@ def nr_softbuffer(max_cb=SRSRAN_SCH_NR_MAX_NOF_CB_LDPC):
     return sb
 
 
+def nr_softbuffer_tx(max_cb=SRSRAN_SCH_NR_MAX_NOF_CB_LDPC, max_cb_size=MAX_CB_SIZE):
+    """A transmit soft buffer with the capacities the reference's NR users give theirs."""
+    return SoftbufferTx(max_cb=max_cb, max_cb_size=max_cb_size)
+
+
 def read_cb8(sb, r, n):
     """n int8 soft bits of code block r (the NR path uses the buffers as int8, sch_nr.c:614)."""
     import torch
@@ -172,16 +191,17 @@ def read_cb8(sb, r, n):
 
 
 class SchNr:
-    """srsran_sch_nr_t (receive side) owner."""
+    """srsran_sch_nr_t owner: a receiver (srsran_sch_nr_init_rx) or, with tx=True, a transmitter (_init_tx)."""
 
-    def __init__(self, nof_prb=52, scaling=0.8, max_nof_iter=10, disable_simd=False, max_mimo_layers=1):
+    def __init__(self, nof_prb=52, scaling=0.8, max_nof_iter=10, disable_simd=False, max_mimo_layers=1, tx=False):
         self.q = srsran_sch_nr_t()
         a = srsran_sch_nr_args_t()
         a.disable_simd = disable_simd
         a.decoder_scaling_factor = scaling
         a.max_nof_iter = max_nof_iter
-        if lib().srsran_sch_nr_init_rx(ctypes.byref(self.q), ctypes.byref(a)) != 0:
-            raise RuntimeError("srsran_sch_nr_init_rx failed (no HIP device?)")
+        init = lib().srsran_sch_nr_init_tx if tx else lib().srsran_sch_nr_init_rx
+        if init(ctypes.byref(self.q), ctypes.byref(a)) != 0:
+            raise RuntimeError("srsran_sch_nr_init failed (no HIP device?)")
         self.carrier = make_carrier(nof_prb, max_mimo_layers)
         lib().srsran_sch_nr_set_carrier(ctypes.byref(self.q), ctypes.byref(self.carrier))
 
@@ -210,6 +230,31 @@ class SchNr:
             arr[i].d_e_bits, arr[i].d_payload = de, dp
             arr[i].new_data = int(ent[4]) if len(ent) > 4 else 0
         return lib().srsran_sch_nr_gpu_decode_batch(ctypes.byref(self.q), len(entries), arr, d_crc, d_avg, stream)
+
+    def set_nof_prb(self, nof_prb):
+        self.carrier.nof_prb = nof_prb
+        lib().srsran_sch_nr_set_carrier(ctypes.byref(self.q), ctypes.byref(self.carrier))
+
+    def encode(self, sb, tbs, R, Qm, G, Nl, rv, payload, lbrm=False, mcs256=False, uplink=False, fill=0):
+        """srsran_dlsch_nr_encode / srsran_ulsch_nr_encode -> (ret, e_bits [G] preset to `fill`)."""
+        cfg = make_cfg(lbrm, mcs256)
+        tb = make_tb(tbs, R, Qm, G, Nl, rv, sb)
+        pl = np.ascontiguousarray(payload, np.uint8)
+        assert pl.size >= tbs // 8
+        e = np.full(max(G, 1), fill, np.uint8)
+        f = lib().srsran_ulsch_nr_encode if uplink else lib().srsran_dlsch_nr_encode
+        ret = f(ctypes.byref(self.q), ctypes.byref(cfg), ctypes.byref(tb), pl.ctypes.data, e.ctypes.data)
+        return ret, e[:G]
+
+    def encode_batch(self, entries, stream=None):
+        """srsran_sch_nr_gpu_encode_batch. entries: list of (cfg, tb, d_payload, d_e_bits); the caller keeps
+        cfg / tb alive until the call returns (descriptors are read during the call)."""
+        arr = (srsran_sch_nr_gpu_enc_t * max(len(entries), 1))()
+        for i, (cfg, tb, dp, de) in enumerate(entries):
+            arr[i].sch_cfg = ctypes.pointer(cfg)
+            arr[i].tb = ctypes.pointer(tb)
+            arr[i].d_payload, arr[i].d_e_bits = dp, de
+        return lib().srsran_sch_nr_gpu_encode_batch(ctypes.byref(self.q), len(entries), arr, stream)
 
     def free(self):
         if self.q.gpu:

@@ -16,6 +16,7 @@
 #include "../../include/srsran_ue_dl.h"
 #include "chest_kernel.h"
 #include "dev_buf.h"
+#include "devkey.h"
 #include "lte_seq_host.h"
 #include "pdsch_internal.h"
 #include "ofdm_kernel.h"
@@ -303,8 +304,7 @@ int srsran_chest_dl_init(srsran_chest_dl_t* q, uint32_t max_prb, uint32_t nof_rx
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   memset(q, 0, sizeof(*q));
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_chest_dl] no HIP device available\n");
     return SRSRAN_ERROR;
   }

@@ -15,6 +15,7 @@
 
 #include "../../include/srsran_enb_dl.h"
 #include "dev_buf.h"
+#include "devkey.h"
 #include "llr_kernel.h"
 #include "pdsch_internal.h"
 
@@ -520,8 +521,7 @@ int srsran_enb_dl_init(srsran_enb_dl_t* q, cf_t* out_buffer[SRSRAN_MAX_PORTS], u
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   memset(q, 0, sizeof(*q));
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_enb_dl] no HIP device\n");
     return SRSRAN_ERROR;
   }

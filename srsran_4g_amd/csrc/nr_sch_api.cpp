@@ -28,6 +28,7 @@
 
 #include "../../include/srsran_sch_nr.h"
 #include "dev_buf.h"
+#include "devkey.h"
 #include "ldpc_internal.h"
 #include "ldpc_enc_kernel.h"
 #include "nr_rm_tx_pos.h"
@@ -691,8 +692,7 @@ static int init_common(srsran_sch_nr_t* q, const srsran_sch_nr_args_t* args, boo
     fprintf(stderr, "[srsran_4g_amd] NR SCH: flooded LDPC schedule not provided on the GPU\n");
     return SRSRAN_ERROR;
   }
-  int dev = 0;
-  if (hipGetDeviceCount(&dev) != hipSuccess || dev == 0) {
+  if (!have_gpu()) {
     (void)hipGetLastError();
     fprintf(stderr, "[srsran_4g_amd] NR SCH: no HIP device available\n");
     return SRSRAN_ERROR;

@@ -322,8 +322,7 @@ int srsran_ofdm_rx_init_cfg(srsran_ofdm_t* q, srsran_ofdm_cfg_t* cfg)
       (cfg->sf_type != SRSRAN_SF_NORM && cfg->sf_type != SRSRAN_SF_MBSFN)) {
     return SRSRAN_ERROR;
   }
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_ofdm] no HIP device available\n");
     return SRSRAN_ERROR;
   }
@@ -535,8 +534,7 @@ int srsran_cfo_init(srsran_cfo_t* h, uint32_t nsamples)
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   memset(h, 0, sizeof(*h));
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_cfo] no HIP device available\n");
     return SRSRAN_ERROR;
   }

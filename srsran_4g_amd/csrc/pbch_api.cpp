@@ -13,6 +13,7 @@
 
 #include "../../include/srsran_pbch.h"
 #include "dev_buf.h"
+#include "devkey.h"
 #include "lte_seq_host.h"
 #include "pbch_kernel.h"
 #include "pdsch_internal.h"
@@ -275,8 +276,7 @@ int srsran_pbch_init(srsran_pbch_t* q)
   }
   memset(q, 0, sizeof(*q));
   q->nof_symbols = PBCH_MAX_SYM;
-  int ndev       = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_pbch] no HIP device\n");
     return SRSRAN_ERROR;
   }

@@ -21,7 +21,7 @@ using namespace srsran_amd;
 
 namespace {
 
-std::mutex g_mu;
+std::mutex g_ctx_mu;
 struct Ctx {  // host-synchronous stage APIs: one stream + scratch per device
   hipStream_t stream = nullptr;
   DevBuf<uint8_t> d_a, d_b;  // bytes, 4096 floor
@@ -40,8 +40,7 @@ bool ctx_ready(Ctx& g_ctx)
   if (g_ctx.stream) {
     return true;
   }
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_phch] no HIP device available\n");
     return false;
   }
@@ -116,7 +115,7 @@ int srsran_demod_soft_demodulate_s(srsran_mod_t modulation, const cf_t* symbols,
   if (nsymbols == 0) {
     return 0;
   }
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
   Ctx&                        g_ctx = ctx_for(cur_dev());
   if (!ctx_ready(g_ctx) || !g_ctx.d_a.reserve((size_t)nsymbols * sizeof(cf_t), kFloor) ||
       !g_ctx.d_b.reserve((size_t)nsymbols * q * sizeof(int16_t), kFloor)) {
@@ -136,7 +135,7 @@ void srsran_sequence_apply_s(const int16_t* in, int16_t* out, uint32_t length, u
   if (length == 0 || !in || !out) {
     return;
   }
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
   Ctx&                        g_ctx = ctx_for(cur_dev());
   const size_t bytes = (size_t)length * sizeof(int16_t);
   if (!ctx_ready(g_ctx) || !g_ctx.d_a.reserve(bytes, kFloor) || !g_ctx.d_b.reserve(bytes, kFloor)) {
@@ -189,7 +188,7 @@ int srsran_predecoding_type(cf_t*              y[4],
   const size_t n   = (size_t)nof_symbols;
   const size_t nin = (size_t)nof_rxant * (1 + nof_ports);  // y + h
   const size_t nout = (size_t)nof_layers;
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
   Ctx&                        g_ctx = ctx_for(cur_dev());
   if (!ctx_ready(g_ctx) || !g_ctx.d_a.reserve(nin * n * sizeof(cf_t), kFloor) ||
       !g_ctx.d_b.reserve(nout * n * (sizeof(cf_t) + sizeof(float)), kFloor)) {

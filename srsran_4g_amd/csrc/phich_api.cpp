@@ -12,6 +12,7 @@
 
 #include "../../include/srsran_phich.h"
 #include "dev_buf.h"
+#include "devkey.h"
 #include "lte_seq_host.h"
 #include "phich_kernel.h"
 
@@ -163,8 +164,7 @@ int srsran_phich_init(srsran_phich_t* q, uint32_t nof_rx_antennas)
   }
   memset(q, 0, sizeof(*q));
   q->nof_rx_antennas = nof_rx_antennas;
-  int ndev           = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_phich] no HIP device\n");
     return SRSRAN_ERROR;
   }

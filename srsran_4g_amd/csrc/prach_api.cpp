@@ -13,6 +13,7 @@
 
 #include "../../include/srsran_prach.h"
 #include "dev_buf.h"
+#include "devkey.h"
 #include "prach_kernel.h"
 
 using namespace srsran_amd;
@@ -354,8 +355,7 @@ int srsran_prach_init(srsran_prach_t* p, uint32_t max_N_ifft_ul)
   }
   memset(p, 0, sizeof(*p));
   p->max_N_ifft_ul = max_N_ifft_ul;
-  int ndev         = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+  if (!have_gpu()) {
     fprintf(stderr, "[srsran_prach] no HIP device\n");
     return SRSRAN_ERROR;
   }

@@ -1037,7 +1037,7 @@ namespace {
 const uint16_t kPucchBasis[SRSRAN_UCI_CQI_CODED_PUCCH_B] = {0x0C03, 0x0E07, 0x1F49, 0x1D0D, 0x1C8F, 0x1DD3, 0x1F55,
                                                             0x1D99, 0x1E9B, 0x1E5D, 0x1EE5, 0x1D67, 0x1FA9, 0x1EAB,
                                                             0x14B1, 0x16F3, 0x1A77, 0x1939, 0x00FB, 0x0061};
-// (32, O) basis sequences, 36.212 Table 5.2.2.6.4-1 (as sch_api.cpp's kBlockBasisHost)
+// (32, O) basis sequences, 36.212 Table 5.2.2.6.4-1 (as uci_host.cpp's kBlockBasisHost)
 const uint16_t kBlockBasis[32] = {0x403, 0x607, 0x749, 0x50D, 0x48F, 0x5D3, 0x755, 0x599, 0x69B, 0x65D, 0x6E5,
                                   0x567, 0x7A9, 0x6AB, 0x4B1, 0x6F3, 0x277, 0x139, 0x0FB, 0x061, 0x445, 0x60B,
                                   0x591, 0x717, 0x3DF, 0x4E3, 0x32D, 0x3AF, 0x175, 0x1FD, 0x7FF, 0x001};

@@ -1,6 +1,6 @@
 // srsran_4g_amd/csrc/pusch_api.cpp -- srsran_pusch_t (include/srsran_pusch.h; pusch.c:108-471): PUSCH receive, its
 // batch, and srsran_pusch_encode, over the kernels of pusch_kernel.hip, llr_kernel.hip, pusch_tx_kernel.hip and the
-// UL-SCH coder of sch_api.cpp; and the transform precoder's entry points (dft_precoding.c).
+// UL-SCH coder of ulsch_api.cpp; and the transform precoder's entry points (dft_precoding.c).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>

@@ -1,7 +1,8 @@
-// srsran_4g_amd/csrc/sch_internal.h -- what the other units of the library call in sch_api.cpp beside the public
-// srsran_sch.h: the UL-SCH decode on device LLRs, its batch and the object's stream (pusch_api.cpp, ue_ul_api.cpp),
-// the UL-SCH transmit step (pusch_api.cpp), the device views of a soft buffer (nr_sch_api.cpp) and the transmitter's
-// rate-matching table.
+// srsran_4g_amd/csrc/sch_internal.h -- what the other units of the library call in the units behind srsran_sch.h
+// beside the public header: the UL-SCH decode on device LLRs and its batch (ulsch_api.cpp) and the object's stream
+// (sch_api.cpp), for pusch_api.cpp and ue_ul_api.cpp; the UL-SCH transmit step (ulsch_api.cpp, for pusch_api.cpp); the
+// device views of a soft buffer (softbuffer_api.cpp, for nr_sch_api.cpp); the transmitter's rate-matching table
+// (rm_turbo_api.cpp).  What those units share among themselves is in sch_units.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -19,7 +19,7 @@ namespace srsran_amd {
 namespace {
 
 std::atomic<bool> g_on{false};
-std::mutex        g_mu;
+std::mutex        g_rec_mu;
 struct Rec {
   int        stage;
   int        dev;
@@ -43,7 +43,7 @@ hipEvent_t take(int dev)
   return e;
 }
 
-void drain()  // caller holds g_mu
+void drain()  // caller holds g_rec_mu
 {
   for (const Rec& r : g_pending) {
     float ms = 0.f;
@@ -94,7 +94,7 @@ StageScope::StageScope(int stage, hipStream_t stream) : stage_(stage), stream_(s
   if (!g_on.load(std::memory_order_relaxed)) {
     return;
   }
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_rec_mu);
   dev_ = cur_dev();
   e0_  = take(dev_);
   if (e0_) {
@@ -107,7 +107,7 @@ StageScope::~StageScope()
   if (!e0_) {
     return;
   }
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_rec_mu);
   hipEvent_t e1 = take(dev_);
   if (!e1) {
     g_pool[dev_].push_back(e0_);
@@ -126,7 +126,7 @@ using namespace srsran_amd;
 
 extern "C" void srsran_amd_timing_enable(int enable)
 {
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_rec_mu);
   drain();
   for (int i = 0; i < ST_COUNT; i++) {
     g_ms[i] = 0;
@@ -140,7 +140,7 @@ extern "C" int srsran_amd_timing_read(float ms[SRSRAN_AMD_NOF_STAGES], uint32_t 
   if (!ms || !launches) {
     return -1;
   }
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_rec_mu);
   drain();
   for (int i = 0; i < ST_COUNT; i++) {
     ms[i]       = (float)g_ms[i];

@@ -88,23 +88,13 @@ struct Config {
   uint16_t* d_trev_nat = nullptr;
 };
 
-std::mutex                             g_mu;
+std::mutex                             g_cfgs_mu;
 std::map<std::tuple<int, uint32_t, int>, Config*> g_cfg;  // (device, K, nsb)
-int                                    g_have_gpu = -1;
-
-bool have_gpu()
-{
-  if (g_have_gpu < 0) {
-    int n = 0;
-    g_have_gpu = (hipGetDeviceCount(&n) == hipSuccess && n > 0) ? 1 : 0;
-  }
-  return g_have_gpu == 1;
-}
 
 // Build (once) the configuration for K decoded with nsb sub-blocks (1 = generic).
 Config* get_config(uint32_t K, int nsb)
 {
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_cfgs_mu);
   auto key = std::make_tuple(cur_dev(), K, nsb);
   auto it  = g_cfg.find(key);
   if (it != g_cfg.end()) {
@@ -240,7 +230,7 @@ std::map<int, XpowTables> g_xpow;  // per device
 // the current device's tables (nullptr if they cannot be built)
 const XpowTables* xpow_tables()
 {
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_cfgs_mu);
   const int dev = cur_dev();
   auto      it  = g_xpow.find(dev);
   if (it != g_xpow.end()) {
@@ -270,7 +260,7 @@ std::map<std::pair<int, uint32_t>, const uint16_t*> g_qpp8;
 
 const uint16_t* qpp8_table(uint32_t K, uint32_t nsb, int idx)
 {
-  std::lock_guard<std::mutex> lk(g_mu);
+  std::lock_guard<std::mutex> lk(g_cfgs_mu);
   const auto                  key = std::make_pair(cur_dev(), K);
   auto                        it  = g_qpp8.find(key);
   if (it != g_qpp8.end()) {
@@ -443,11 +433,7 @@ uint32_t srsran_tdec_autoimp_get_subblocks_8bit(uint32_t long_cb)
   return 0;
 }
 
-int srsran_tdec_gpu_available(void)
-{
-  std::lock_guard<std::mutex> lk(g_mu);
-  return have_gpu() ? 1 : 0;
-}
+int srsran_tdec_gpu_available(void) { return have_gpu() ? 1 : 0; }
 
 const char* srsran_tdec_gpu_kernel_name(uint32_t long_cb)
 {
@@ -530,12 +516,9 @@ int srsran_tdec_init_manual(srsran_tdec_t* h, uint32_t max_long_cb, srsran_tdec_
   if (max_long_cb > SRSRAN_TCOD_MAX_LEN_CB) {
     return SRSRAN_ERROR;
   }
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!have_gpu()) {
-      fprintf(stderr, "[srsran_tdec] no HIP device available\n");
-      return SRSRAN_ERROR;
-    }
+  if (!have_gpu()) {
+    fprintf(stderr, "[srsran_tdec] no HIP device available\n");
+    return SRSRAN_ERROR;
   }
   Ctx* c = new Ctx();
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||

@@ -133,12 +133,6 @@ const RmTxTab* rm_tab(uint32_t cb_idx)
   }
   return &(g_tabs[key] = t);
 }
-
-bool have_device()
-{
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
 }  // namespace
 
 extern "C" {
@@ -149,7 +143,7 @@ int srsran_tcod_init(srsran_tcod_t* h, uint32_t max_long_cb)
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
   memset(h, 0, sizeof(*h));
-  if (!have_device()) {
+  if (!srsran_amd::have_gpu()) {
     fprintf(stderr, "[srsran_tcod] no HIP device\n");
     return SRSRAN_ERROR;
   }
@@ -208,7 +202,7 @@ int srsran_rm_turbo_tx_lut(uint8_t* w_buff, uint8_t* systematic, uint8_t* parity
       (rv_idx == 0 && (!systematic || !parity))) {
     return SRSRAN_ERROR_INVALID_INPUTS;
   }
-  if (!have_device()) {
+  if (!srsran_amd::have_gpu()) {
     fprintf(stderr, "[srsran_rm_turbo] no HIP device\n");
     return SRSRAN_ERROR;
   }

@@ -166,7 +166,16 @@ def test_dlsch_max_noi(S, q, ora, max_iter):
     check_tb(S, q, ora, sb, tbs, Qm, 0, llr, eff, None, max_iter)
 
 
-def test_dlsch_input_checks(S, q, ora):
+def test_dlsch_input_checks(S, q, ora, monkeypatch):
+    # the checks the synchronous decode shares with the batch path (check_tb): tbs = 40 is one block of K = 64.
+    # Expected values: what the commit before the two were merged returned, read from its code and confirmed by one
+    # run of its library -- rv = 4 passed dlsch_decode_sync's own checks and was refused by check_tb's 'tb.rv > 3'
+    # inside the batch (SRSRAN_ERROR_INVALID_INPUTS, written to the result by tb_launch's status branch); a
+    # modulation of no bits was refused by dlsch_decode_sync's 'Qm == 0' (SRSRAN_ERROR_INVALID_INPUTS).
+    one = S.SoftbufferRx(max_cb=1)
+    assert q.decode(one, 40, 2, 4, np.zeros(300, np.int16))[0] == -2   # rv > 3 (sch.c:540-546)
+    monkeypatch.setitem(S.MOD_FROM_QM, 0, 5)                           # srsran_mod_t 5: srsran_mod_bits_x_symbol = 0
+    assert q.decode(one, 40, 0, 0, np.zeros(300, np.int16))[0] == -2   # Qm == 0 (sch.c:524-529)
     sb = S.SoftbufferRx(nof_prb=100)
     llr = np.zeros(3000, np.int16)
     assert q.decode(sb, 0, 2, 0, llr)[0] == 0      # tbs == 0: nothing to do (sch.c:531-533)

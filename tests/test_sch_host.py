@@ -1,8 +1,9 @@
 """CPU tests of the DL-SCH host logic in the product library (no GPU needed).
 
 srsran_cbsegm / cbsize / cbindex and the CRC utilities are host code of
-srsran_4g_amd/csrc/sch_api.cpp (cbsegm.c:62-151, crc.c:69-195); they are checked
-against the oracle (itself pinned to the reference, tests/test_sch_oracle.py).
+srsran_4g_amd/csrc/fec_host.cpp (cbsegm.c:62-151, crc.c:69-195); they are checked
+through the shared library against the oracle (itself pinned to the reference,
+tests/test_sch_oracle.py); tests/test_sch_fec_host.py runs the same unit under sanitizers.
 Every device entry point must fail loudly without a HIP device.
 """
 import ctypes

@@ -115,10 +115,10 @@ Config* get_config(uint32_t K, int nsb)
     a.xyw = nsb * a.Ls;
     a.M   = (a.L + TDEC_W - 1) / TDEC_W;
   } else {
-    a.L   = K;
-    a.Ls  = (K + 3) | 1u;
+    a.L   = K;  // the generic decoder's workgroup: tdec_gen_geo.h
+    a.Ls  = tdec_gen_xyw(K);
     a.xyw = a.Ls;
-    a.M   = (K + 3 + TDEC_W - 1) / TDEC_W;
+    a.M   = tdec_gen_M(K);
   }
   a.magicL  = (uint32_t)(((1ull << 32) + a.L - 1) / a.L);
   a.magicLs = (uint32_t)(((1ull << 32) + a.Ls - 1) / a.Ls);
@@ -594,7 +594,7 @@ void srsran_tdec_iteration(srsran_tdec_t* h, int16_t* input, uint8_t* output)
     fprintf(stderr, "[srsran_tdec] unsupported K=%u\n", K);
     return;
   }
-  const size_t st = 2 * (size_t)c->proto.xyw;
+  const size_t st = c->nsb == 1 ? tdec_gen_state_len(K) : 2 * (size_t)c->proto.xyw;
   if (!ctx->d_state.reserve(st)) {
     return;
   }

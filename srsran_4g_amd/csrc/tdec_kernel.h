@@ -5,9 +5,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "tdec_gen_geo.h"
+
 namespace srsran_amd {
 
-static constexpr int TDEC_W       = 32;  // beta checkpoint window (must match the kernel)
+static constexpr int TDEC_W       = 32;  // beta checkpoint window of the window classes (generic: tdec_gen_geo.h)
 static constexpr int TDEC_OVERLAP = 40;  // sliding-window training length
 
 // One code block of a DL-SCH decode (launch-index order).
@@ -38,7 +40,7 @@ struct TdecArgs {
   const uint16_t* trev;      // slot of pi^-1(n(q)) (device, K entries, q order)
   const uint16_t* tfwd_nat;  // slot of pi(n)       (device, K entries, natural order)
   const uint16_t* trev_nat;  // slot of pi^-1(n)    (device, K entries, natural order)
-  short*          state;     // optional ncb * 2 * xyw saved LLR/AUX state (device) or nullptr
+  short*          state;     // optional saved state (device) or nullptr: ncb * 2 * xyw LLR/AUX, generic: ncb * xyw S
   uint32_t        L;         // sub-block length (K for the generic decoder)
   uint32_t        Ls;        // LDS slot stride per sub-block
   uint32_t        xyw;       // LDS words per code block

@@ -13,6 +13,9 @@
 //     states, v_perm_b32 (per-lane selector) arranges them, v_pk_add_i16 (clamp)
 //     adds the branch metrics, v_pk_max_i16 selects.
 //   * NSB=16: one CB per wave (16 quads); NSB=8: two CBs; generic (NSB=1): 16 CBs.
+//   * the generic decoder keeps the mapping and the schedule below but has its own body (tdec1_body: one
+//     int16 a slot in LDS, 16-step windows fed from the input a window ahead, eight workgroups a CU); the
+//     next three points describe the window decoders' (tdec_body).
 //   * per CB, LDS holds XY[slot] = (x, y) branch inputs of the current constituent
 //     decoder and AUX[slot] (ext1 / app1 bookkeeping of turbodecoder_iter.h); after a
 //     constituent decode XY.lo is overwritten with its output LLR.  The QPP
@@ -29,6 +32,7 @@
 
 #include "crc24_dev.h"
 #include "tdec_kernel.h"
+#include "tdec_gen_geo.h"
 #include "stage_timing.h"
 
 namespace srsran_amd {
@@ -653,11 +657,6 @@ __device__ __forceinline__ void tdec_body(const TdecArgs& a, int bid)
           xyc[sl]        = pack2(x, p0);
         });
       }
-      if constexpr (NSB == 1) {
-        if (t2 < 3) {
-          xyc[K + t2] = pack2(st[t2], p0t[t2]);
-        }
-      }
     } else {
       for (int p = t2; p < K; p += G2) {  // ext1 -= app1 (h > 1), keep it in AUX
         const int   sl = pslot(p);
@@ -667,11 +666,6 @@ __device__ __forceinline__ void tdec_body(const TdecArgs& a, int bid)
       __syncthreads();
       // app2 = ext1 interleaved
       for_chunks(h, [&](int p, short, short, short p1, int t) { xyc[pslot(p)] = pack2(auxc[t], p1); });
-      if constexpr (NSB == 1) {
-        if (t2 < 3) {
-          xyc[K + t2] = pack2(x2t[t2], p1t[t2]);
-        }
-      }
     }
     __syncthreads();
 
@@ -748,16 +742,534 @@ __device__ __forceinline__ void tdec_body(const TdecArgs& a, int bid)
   }
 }
 
-template <int NSB, bool ES>
-__global__ __launch_bounds__(128, 2) void tdec_kernel(TdecArgs a)
+// ======================= generic decoder (NSB = 1, K <= 400) =======================
+// The same quad mapping, trellis steps and crossover schedule, on a quarter of the LDS and half the
+// window registers, so that eight workgroups fit a CU:
+//   * LDS per block is ONE int16 array S (tdec16_kernel.hip's bookkeeping, all wrapping here):
+//       DEC1 at position p:               x = syst + S[p],  y = parity0,  S[p] <- out1 - S[p]
+//       DEC2 at position p, b = pi(p):    x = S[b],         y = parity1,  S[b] <- out2 - S[b]
+//     plus the checkpoints (a window is GW = 16 steps) and a decision bitmap the LLR signs are ORed into.
+//   * systematic / parity values are not staged: lane j of the quad loads the 24 input bytes of positions
+//     t0 + 4j .. t0 + 4j + 3 of the NEXT window (and DEC2's four pi slots) while the current one runs, packs
+//     its four (x, y) when the window starts and the quad shares them with one DPP quad_perm a position.
+//     The three tail positions K .. K + 2 follow position K - 1 in the natural layout as (x, y) pairs
+//     of DEC1 then DEC2, so the lane whose four positions start at K gets them from the same 24 bytes.
+//   * the LLR of a position is the same in the four lanes; its owner keeps it and, when the window ends,
+//     writes its four S values and decision bits.  Within a half-iteration S[p] is written only by the side
+//     that emits p's LLR, after both sides' last read of it (phase 1 ends at the barrier, and a phase-2
+//     window belongs to one side).
+namespace gen {
+
+constexpr int GW = TDEC_GEN_W;
+
+struct Lane1 {
+  const short*    in;    // this block's input, natural layout (3K + 12 int16)
+  const uint16_t* tf;    // pi(p), natural order
+  short*          S;     // this block's S (LDS)
+  uint32_t*       ck;    // the workgroup's checkpoints [M][64] (LDS)
+  uint32_t*       bits;  // this block's decision bitmap (LDS)
+  int             K, j, lane;
+  LaneSel         ls;
+};
+
+// Opaque copy of a per-lane value.  Every address of a window derives from the quad position j or the block's
+// place in LDS; taken through this at the window, none of them is hoisted out of the window and half-iteration
+// loops (loop-invariant code motion would keep some thirty of them in registers across the decode).
+__device__ __forceinline__ int fresh(int v)
 {
-  tdec_body<NSB, ES>(a, blockIdx.x);
+  asm volatile("" : "+v"(v));
+  return v;
+}
+template <class T>
+__device__ __forceinline__ T* fresh_lds(T* p)
+{
+  typedef T __attribute__((address_space(3)))* lptr;
+  return (T*)(lptr)(size_t)(uint32_t)fresh((int)(uint32_t)(size_t)(lptr)p);
+}
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef const u32x2 __attribute__((address_space(1)))* gu32x2p;  // global (not flat) loads
+
+// The owner's part of a window as loaded: 12 int16 (S, P0, P1 of four positions) and DEC2's four pi slots.
+struct Raw1 {
+  u32x2 w0, w1, w2, t;
+};
+// The owner's four positions of the running window: packed (x, y), and what the S update needs
+// (DEC1: the S read; DEC2: the pi slot -- the S read there is x).
+struct Own1 {
+  uint32_t xy[4], aux[4];
+};
+
+template <bool D2>
+__device__ __forceinline__ void issue(const Lane1& c, Raw1& r, int t0)
+{
+  const int     p4 = min(t0 + 4 * fresh(c.j), c.K);  // past the tail: the tail again (unused)
+  const gu32x2p b  = (gu32x2p)(c.in + 3 * p4);
+  r.w0             = b[0];
+  r.w1             = b[1];
+  r.w2             = b[2];
+  if (D2) {
+    r.t = *(gu32x2p)(c.tf + min(p4, c.K - 4));
+  }
+}
+
+template <int JJ>
+__device__ __forceinline__ void spread(const uint32_t* xy, uint32_t* xw)
+{
+#pragma unroll
+  for (int v = 0; v < 4; v++) {
+    xw[4 * JJ + v] = v2u(dpp<QP(JJ, JJ, JJ, JJ)>(u2v(xy[v])));
+  }
+}
+
+// Window sequence of one side with the loads of the next window in flight.
+//   alpha side: windows 0, 1, ..., Ma - 1;  beta side: Mb - 1, ..., 1, 0
+template <bool D2>
+struct Pipe1 {
+  Raw1 g;
+  int  nwin;
+  bool beta;
+
+  __device__ __forceinline__ int  t0_of(int idx) const { return (beta ? nwin - 1 - idx : idx) * GW; }
+  __device__ __forceinline__ void load(const Lane1& c, int idx)
+  {
+    if (idx < nwin) {
+      issue<D2>(c, g, t0_of(idx));
+    }
+  }
+  // window idx begins: the owner packs its four positions, the quad shares them; the loads of idx + 1 go out.
+  __device__ __forceinline__ void next(const Lane1& c, int idx, uint32_t* xw, Own1& o)
+  {
+    const int      p4   = t0_of(idx) + 4 * fresh(c.j);
+    const bool     real = p4 < c.K;  // else tail (p4 == K) or unused
+    const short*   S    = fresh_lds(c.S);
+    const uint32_t e[6] = {g.w0.x, g.w0.y, g.w1.x, g.w1.y, g.w2.x, g.w2.y};
+    auto el = [&](int k) -> uint32_t { return (k & 1) ? (e[k >> 1] >> 16) : (e[k >> 1] & 0xffffu); };
+    if (D2) {
+      const uint32_t b[4] = {g.t.x & 0xffffu, g.t.x >> 16, g.t.y & 0xffffu, g.t.y >> 16};
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        const uint32_t x = (uint16_t)S[b[v]];
+        o.aux[v]         = b[v];
+        o.xy[v]          = real ? (x | (el(3 * v + 2) << 16)) : e[v < 2 ? 3 + v : 5];
+      }
+    } else {
+      const uint2    sv   = *reinterpret_cast<const uint2*>(S + min(p4, c.K - 4));
+      const uint32_t s[4] = {sv.x & 0xffffu, sv.x >> 16, sv.y & 0xffffu, sv.y >> 16};
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        o.aux[v] = s[v];
+        o.xy[v]  = real ? (((el(3 * v) + s[v]) & 0xffffu) | (el(3 * v + 1) << 16)) : e[v < 3 ? v : 2];
+      }
+    }
+    load(c, idx + 1);
+    spread<0>(o.xy, xw);
+    spread<1>(o.xy, xw);
+    spread<2>(o.xy, xw);
+    spread<3>(o.xy, xw);
+  }
+};
+
+// A position's branch metrics depend on its input alone, so the scheduler would compute those of a whole
+// window ahead of the recursion and keep them (48 registers).  An opaque move of the input together with the
+// running state keeps each position's metrics next to its step; they still overlap the step's two DPP reads.
+__device__ __forceinline__ v2s at_step(uint32_t* xw, int i, v2s& P)
+{
+  uint32_t p = v2u(P);
+  asm volatile("" : "+v"(xw[i]), "+v"(p));
+  P = u2v(p);
+  return u2v(xw[i]);
+}
+
+// The LLR of window position i (the same in the four lanes) goes to its owner.
+__device__ __forceinline__ void keep(const Lane1& c, uint32_t* ow, int i, short o)
+{
+  ow[i & 3] = c.j == (i >> 2) ? (uint32_t)(uint16_t)o : ow[i & 3];
+}
+
+__device__ __forceinline__ uint32_t bit_of(int n, uint32_t o)
+{
+  return (uint32_t)((short)o > 0) << (((n >> 3) & 3) * 8 + 7 - (n & 7));
+}
+
+// The window at t0 ends: the owner's S updates (vec_sub, wraps) and, when the half-iteration's decision is
+// needed, its bits (turbodecoder.c:370-378: the sign of ext1 after DEC1, of app1 after DEC2).
+template <bool D2, bool BITS>
+__device__ __forceinline__ void emit(const Lane1& c, int t0, const Own1& o, const uint32_t* ow)
+{
+  const int p4   = t0 + 4 * fresh(c.j);
+  short*    S    = fresh_lds(c.S);
+  uint32_t* bits = fresh_lds(c.bits);
+  if (p4 < c.K) {
+    if (D2) {
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        S[o.aux[v]] = (short)(ow[v] - o.xy[v]);
+        if (BITS) {
+          atomicOr(&bits[o.aux[v] >> 5], bit_of((int)o.aux[v], ow[v]));
+        }
+      }
+    } else {
+      uint32_t d[4];
+      uint32_t word = 0;
+#pragma unroll
+      for (int v = 0; v < 4; v++) {
+        d[v] = (ow[v] - o.aux[v]) & 0xffffu;
+        word |= bit_of(p4 + v, ow[v]);
+      }
+      *reinterpret_cast<uint2*>(S + p4) = make_uint2(d[0] | (d[1] << 16), d[2] | (d[3] << 16));
+      if (BITS) {
+        atomicOr(&bits[p4 >> 5], word);
+      }
+    }
+  }
+}
+
+// The four window bodies of tdec_kernel.hip's crossover schedule on a window held in registers.
+
+// K is a multiple of 8 and a window starts at a multiple of GW = 16, so the partial windows have two
+// shapes only: the top window holds the tail alone (TOP_TAIL = 3 positions, K % 16 == 0) or the last
+// eight positions and the tail (TOP_HALF = 11, K % 16 == 8).
+constexpr int TOP_TAIL = 3, TOP_HALF = 11;
+
+// Backward over the NP positions p0+NP-1 .. p0; the stored beta[p0] goes to slot m-1 when store_ck.
+template <int NP>
+__device__ __forceinline__ v2s beta_window(const Lane1& c, v2s P, uint32_t* xw, int p0, int m, bool store_ck,
+                                           v2s& stored)
+{
+#pragma unroll
+  for (int i = NP - 1; i >= 0; i--) {
+    P = beta_step<false>(P, at_step(xw, i, P), c.ls);
+    if (i == 0) {
+      stored = P;
+      if (store_ck) {
+        c.ck[(m - 1) * 64 + c.lane] = v2u(P);
+      }
+    }
+    if (beta_norm_at<1>(p0 + i, c.K)) {
+      P = norm<false>(P);
+    }
+  }
+  return P;
+}
+
+// Phase-1 alpha-only window (entry checkpoint in slot ma).
+__device__ __forceinline__ v2s alpha_fw_window(const Lane1& c, v2s P, uint32_t* xw, int t0, int ma)
+{
+  c.ck[ma * 64 + c.lane] = v2u(P);
+#pragma unroll
+  for (int i = 0; i < GW; i++) {
+    v2s c0, c1;
+    alpha_cand<false>(P, at_step(xw, i, P), c.ls, c0, c1);
+    P = pmax(c0, c1);
+    if (alpha_norm_at<1>(t0 + i)) {
+      P = norm<false>(P);
+    }
+  }
+  return P;
+}
+
+// Phase-2 alpha side: beta[t0+1 .. cc] recomputed from the checkpoint at cc, then alpha + LLR of t0 .. ta-1
+// (FULL: cc = ta = t0 + GW; else the TOP_HALF window: cc = K + 3 = t0 + 11, ta = K = t0 + 8).
+template <bool FULL>
+__device__ __forceinline__ v2s alpha_window(const Lane1& c, v2s P, uint32_t* xw, uint32_t* ow, int t0, v2s ckv)
+{
+  constexpr int NA = FULL ? GW : TOP_HALF - 3;
+  constexpr int ic = (FULL ? GW : TOP_HALF) - 1;
+  const int     cc = t0 + ic + 1;
+  v2s           bw[ic + 1];
+  v2s           Pb = ckv;
+  uint32_t      opend = 0;
+#pragma unroll
+  for (int i = ic; i >= 0; i--) {
+    if (i == ic) {
+      bw[i] = Pb;
+      if (FULL && beta_norm_at<1>(cc, c.K)) {
+        Pb = norm<false>(Pb);
+      }
+    } else {
+      Pb    = beta_step<false>(Pb, at_step(xw, i + 1, Pb), c.ls);
+      bw[i] = Pb;
+      if (beta_norm_at<1>(t0 + 1 + i, c.K)) {
+        Pb = norm<false>(Pb);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NA; i++) {
+    v2s c0, c1;
+    alpha_cand<false>(P, at_step(xw, i, P), c.ls, c0, c1);
+    const short o = llr_out<false>(bw[i], c0, c1);
+    P             = pmax(c0, c1);
+    if (alpha_norm_at<1>(t0 + i)) {
+      P = norm<false>(P);
+    }
+    // the LLR is off the recursion: it may trail it by one step, not by a window of live candidates
+    if (i > 0) {
+      uint32_t pw = v2u(P);
+      asm volatile("" : "+v"(opend), "+v"(pw));
+      P = u2v(pw);
+      keep(c, ow, i - 1, (short)opend);
+    }
+    opend = (uint16_t)o;
+  }
+  keep(c, ow, NA - 1, (short)opend);
+  return P;
+}
+
+// Phase-2 beta side, full window at t0: alpha candidates of every position from the entry checkpoint, then
+// beta backward with the LLRs.  Bst = the stored beta of the position above.
+__device__ __forceinline__ v2s beta_llr_window(const Lane1& c, v2s P, v2s& Bst, uint32_t* xw, uint32_t* ow, int t0,
+                                               v2s cka)
+{
+  v2s cw0[GW], cw1[GW];
+  v2s a = cka;
+#pragma unroll
+  for (int i = 0; i < GW; i++) {
+    alpha_cand<false>(a, at_step(xw, i, a), c.ls, cw0[i], cw1[i]);
+    if (i < GW - 1) {
+      a = pmax(cw0[i], cw1[i]);
+      if (alpha_norm_at<1>(t0 + i)) {
+        a = norm<false>(a);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = GW - 1; i >= 0; i--) {
+    keep(c, ow, i, llr_out<false>(Bst, cw0[i], cw1[i]));
+    P   = beta_step<false>(P, at_step(xw, i, P), c.ls);
+    Bst = P;
+    if (beta_norm_at<1>(t0 + i, c.K)) {
+      P = norm<false>(P);
+    }
+  }
+  return P;
+}
+
+// One constituent MAP decode of this quad's block; wave 0 = alpha side, wave 1 = beta side (map_decode).
+template <bool D2, bool BITS>
+__device__ __forceinline__ void map1(const Lane1& c, int wave, int M)
+{
+  const int K  = c.K;
+  const int Nb = K + 3;
+  const int Ma = (K + GW - 1) / GW;
+  const int h  = max(1, min((Nb + GW) / (2 * GW), K / GW));
+  Pipe1<D2> pp;
+  pp.beta = wave != 0;
+  pp.nwin = pp.beta ? M : Ma;
+  uint32_t xw[GW];
+  uint32_t ow[4] = {0, 0, 0, 0};
+  Own1     own;
+  pp.load(c, 0);
+  if (wave == 0) {
+    // ---------------- alpha side ----------------
+    v2s P = init_known(c.j);
+#pragma unroll 1
+    for (int ma = 0; ma < h; ma++) {  // phase 1: windows [0, h), entry checkpoints in slots 0..h-1
+      pp.next(c, ma, xw, own);
+      P = alpha_fw_window(c, P, xw, ma * GW, ma);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int ma = h; ma < K / GW; ma++) {  // phase 2: windows [h, Ma) with beta recompute + LLR
+      const int t0 = ma * GW;
+      pp.next(c, ma, xw, own);
+      P = alpha_window<true>(c, P, xw, ow, t0, u2v(c.ck[ma * 64 + c.lane]));
+      emit<D2, BITS>(c, t0, own, ow);
+    }
+    if (Ma > K / GW) {  // the last eight positions, with the tail above them
+      const int ma = Ma - 1, t0 = ma * GW;
+      pp.next(c, ma, xw, own);
+      alpha_window<false>(c, P, xw, ow, t0, u2v(c.ck[ma * 64 + c.lane]));
+      emit<D2, BITS>(c, t0, own, ow);
+    }
+  } else {
+    // ---------------- beta side ----------------
+    v2s P                      = init_known(c.j);
+    c.ck[(M - 1) * 64 + c.lane] = v2u(P);  // beta[K + 3]
+    v2s Bst                    = P;
+    int mb                     = M - 1;
+    pp.next(c, 0, xw, own);  // the top window is always partial
+    if (K & 8) {
+      P = beta_window<TOP_HALF>(c, P, xw, mb * GW, mb, mb > h, Bst);
+    } else {
+      P = beta_window<TOP_TAIL>(c, P, xw, mb * GW, mb, mb > h, Bst);
+    }
+    mb--;
+#pragma unroll 1
+    for (; mb >= h; mb--) {  // phase 1: windows [h, M), checkpoints in slots h..M-1
+      pp.next(c, M - 1 - mb, xw, own);
+      P = beta_window<GW>(c, P, xw, mb * GW, mb, mb > h, Bst);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (mb = h - 1; mb >= 0; mb--) {  // phase 2: windows [0, h) with alpha recompute + LLR
+      pp.next(c, M - 1 - mb, xw, own);
+      P = beta_llr_window(c, P, Bst, xw, ow, mb * GW, u2v(c.ck[mb * 64 + c.lane]));
+      emit<D2, BITS>(c, mb * GW, own, ow);
+    }
+  }
+}
+
+}  // namespace gen
+
+template <bool ES>
+__device__ __forceinline__ void tdec1_body(const TdecArgs& a, int bid)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  constexpr int CPW = TDEC_GEN_CPW;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int cw   = lane >> 2;       // block within the workgroup
+  const int j    = lane & 3;        // state-pair index
+  const int t2   = wave * 4 + j;    // thread within the block (both waves), 0..7
+  const int K    = (int)a.K;
+  const int M    = (int)a.M;
+  const TdecGenGeo g = tdec_gen_geo(a.K, a.M);
+  const int cb   = bid * CPW + cw;
+  const int cbl  = cb < (int)a.ncb ? cb : (int)a.ncb - 1;
+  const bool live = cb < (int)a.ncb && (!ES || a.cbs[cbl].slot != TDEC_PAD_SLOT);
+  bool done      = ES && (!live || *a.cbs[cbl].skip);
+
+  gen::Lane1 c;
+  c.in   = ES ? a.cbs[cbl].in : a.in + (size_t)cbl * a.in_stride;
+  c.tf   = a.tfwd_nat;
+  c.S    = reinterpret_cast<short*>(smem) + cw * K;
+  c.ck   = smem + g.s_dw;
+  c.bits = c.ck + g.ck_dw + cw * g.bits_dw;
+  c.K    = K;
+  c.j    = j;
+  c.lane = lane;
+  c.ls   = lane_sel(j);
+  uint32_t*      red   = smem + g.s_dw + g.ck_dw + CPW * g.bits_dw;  // [CPW][2] CRC partials per wave
+  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(c.bits);
+
+  if constexpr (ES) {
+    if (live && done && t2 == 0) {  // skipped block (sch.c:392, 476-480)
+      const uint32_t slot = a.cbs[cbl].slot;
+      a.noi_out[slot]     = 0;
+      a.crc_ok[slot]      = 1;
+    }
+  }
+  // S: no a-priori information before the first half-iteration, or the state a previous launch saved
+  // (srsran_tdec_iteration)
+  if (a.n_start > 0) {
+    const short* se = a.state + (size_t)cbl * K;
+    for (int i = t2; i < K; i += 8) {
+      c.S[i] = se[i];
+    }
+  } else {
+    for (int i = threadIdx.x; i < (int)g.s_dw; i += 128) {
+      smem[i] = 0u;
+    }
+  }
+  const int h_end = (ES && __syncthreads_or(!done) == 0) ? a.n_start : a.n_end;
+#pragma unroll 1
+  for (int h = a.n_start; h < h_end; h++) {
+    const bool crc_now = ES && h + 1 >= a.min_iters;  // early-stop check (sch.c:433)
+    const bool bits    = crc_now || h + 1 == h_end;   // decisions: where the early stop looks, and the last
+    for (int i = threadIdx.x; i < CPW * (int)g.bits_dw; i += 128) {
+      smem[g.s_dw + g.ck_dw + i] = 0u;
+    }
+    __syncthreads();
+    if (h & 1) {
+      if (bits) {
+        gen::map1<true, true>(c, wave, M);
+      } else {
+        gen::map1<true, false>(c, wave, M);
+      }
+    } else {
+      if (bits) {
+        gen::map1<false, true>(c, wave, M);
+      } else {
+        gen::map1<false, false>(c, wave, M);
+      }
+    }
+    __syncthreads();
+
+    // -------- DL-SCH early stop: CRC of the hard decision (sch.c:426-456) --------
+    if constexpr (ES) {
+      if (crc_now) {
+        // opaque copies: nothing of the check is computed ahead of the half-iteration loop and kept across the decode
+        const int      t2     = gen::fresh(wave * 4 + j);
+        const int      cbl    = gen::fresh(cb < (int)a.ncb ? cb : (int)a.ncb - 1);
+        const uint8_t* bytes  = reinterpret_cast<const uint8_t*>(gen::fresh_lds(c.bits));
+        const int      nbytes = K / 8;
+        const int      bpt    = (nbytes + 7) / 8;
+        const int      b0     = t2 * bpt;
+        const int      b1     = min(b0 + bpt, nbytes);
+        const bool     crc_a  = a.cbs[cbl].crc_a;
+        const uint32_t poly   = crc_a ? LTE_CRC24A : LTE_CRC24B;
+        uint32_t       crc    = 0;
+#pragma unroll 1
+        for (int b = b0; b < b1; b++) {
+          crc = crc24_byte(crc, bytes[b], poly);
+        }
+        uint32_t part = b0 < nbytes ? clmul_mod24(crc, (crc_a ? a.xpow_a : a.xpow_b)[nbytes - b1], poly) : 0;
+        part ^= (uint32_t)__shfl_xor((int)part, 1, 64);
+        part ^= (uint32_t)__shfl_xor((int)part, 2, 64);
+        if (j == 0) {
+          red[cw * 2 + wave] = part;
+        }
+        __syncthreads();
+        const bool ok = (red[cw * 2] ^ red[cw * 2 + 1]) == 0;
+        if (ok && !done && live) {
+          const uint32_t slot = a.cbs[cbl].slot;
+          uint8_t*       out  = a.out + (size_t)slot * a.out_stride;
+          for (int b = t2; b < nbytes; b += 8) {
+            out[b] = bytes[b];
+          }
+          if (t2 == 0) {
+            a.noi_out[slot] = (uint8_t)(h + 1);
+            a.crc_ok[slot]  = 1;
+          }
+        }
+        done = done || ok;
+      }
+      if (__syncthreads_or(!done) == 0) {
+        break;  // every code block of this workgroup has passed its CRC
+      }
+    }
+  }
+
+  // -------- hard decision of the last half-iteration (turbodecoder.c:370-378), natural bit order --------
+  if (live && !done && h_end > a.n_start) {
+    const int cbm = ES ? (int)a.cbs[cbl].slot : cbl;  // output / state slot
+    uint8_t*  out = a.out + (size_t)cbm * (ES ? a.out_stride : K / 8);
+    for (int b = t2; b < K / 8; b += 8) {
+      out[b] = bytes[b];
+    }
+    if (ES && t2 == 0) {
+      a.noi_out[cbm] = (uint8_t)a.n_end;
+      a.crc_ok[cbm]  = 0;
+    }
+    if (a.state) {
+      short* se = a.state + (size_t)cbm * K;
+      for (int i = t2; i < K; i += 8) {
+        se[i] = c.S[i];
+      }
+    }
+  }
+}
+
+// Waves a SIMD the kernels are built for: four of the generic decoder (eight workgroups a CU, 20 KB of LDS
+// and at most 128 registers each), two of the window decoders.
+template <int NSB>
+constexpr int kWavesPerSimd = NSB == 1 ? 4 : 2;
+
+template <int NSB, bool ES>
+__global__ __launch_bounds__(128, kWavesPerSimd<NSB>) void tdec_kernel(TdecArgs a)
+{
+  if constexpr (NSB == 1) {
+    tdec1_body<ES>(a, blockIdx.x);
+  } else {
+    tdec_body<NSB, ES>(a, blockIdx.x);
+  }
 }
 
 // Several code-block sizes of one decoder class in one launch: workgroup b belongs to the group
 // g with first[g] <= b < first[g + 1] (descriptors in device memory, read with scalar loads).
 template <int NSB>
-__global__ __launch_bounds__(128, 2) void tdec_multi_kernel(const TdecArgs* __restrict__ groups,
+__global__ __launch_bounds__(128, kWavesPerSimd<NSB>) void tdec_multi_kernel(const TdecArgs* __restrict__ groups,
                                                             const uint32_t* __restrict__ first, int ngroups)
 {
   const uint32_t b  = blockIdx.x;
@@ -771,7 +1283,11 @@ __global__ __launch_bounds__(128, 2) void tdec_multi_kernel(const TdecArgs* __re
     }
   }
   const TdecArgs a = groups[lo];
-  tdec_body<NSB, false>(a, (int)(b - first[lo]));
+  if constexpr (NSB == 1) {
+    tdec1_body<false>(a, (int)(b - first[lo]));
+  } else {
+    tdec_body<NSB, false>(a, (int)(b - first[lo]));
+  }
 }
 
 hipError_t tdec_multi_launch(int nsb, const TdecArgs* d_groups, const uint32_t* d_first, int ngroups,
@@ -832,6 +1348,9 @@ hipError_t tdec_quad_launch(int nsb, const TdecArgs& a, hipStream_t stream)
 
 size_t tdec_lds_bytes(int nsb, int xyw, int M)
 {
+  if (nsb == 1) {  // xyw = K
+    return (size_t)tdec_gen_geo((uint32_t)xyw, (uint32_t)M).total_dw * 4;
+  }
   const int cpw = 64 / (4 * nsb);
   return (size_t)cpw * xyw * 4 + (((size_t)cpw * xyw + 1) / 2) * 4 + (size_t)M * 64 * 4 + (size_t)cpw * 2 * 4;
 }
